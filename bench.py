@@ -14,6 +14,11 @@ scaling); for N > 1 every rank's log-likelihood batch is gathered to rank 0
 with RCCL over xGMI (torch.distributed "nccl"), overlapped with the next step.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for every field.
+
+A plain run sets up, warms up, times the K steps and prints the line.  The
+legs that take runs of their own -- the CPU baseline, C5's int8-against-fp32
+comparison -- run only with --full; --dump-outputs DIR writes what the last
+timed step computed, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -95,7 +100,16 @@ def parse(argv=None):
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--cpu-utts", type=int, default=32, help="distinct utterances in the CPU baseline sample")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="minimum wall time of the CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run the legs the headline figure does not need: the CPU "
+                         "baseline (about --cpu-seconds of host work) and, for c5, the int8-against-fp32 "
+                         "comparison.  Without it the line's cpu_baseline and int8_vs_fp32 are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy in "
+                         "float32 (c3 / c4 / c5: loglik, the step's log-likelihood rows; c2: fbank, its feature "
+                         "rows; at most 60 MB per array: of a larger one a fixed, seeded sample of rows, in row "
+                         "order).  Rank r > 0 writes <name>.rank<r>.npy")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event kernel timing")
     ap.add_argument("--step-times", action="store_true",
                     help="C3: print each timed step's completion time (ms after the window opens) to stderr")
@@ -542,6 +556,26 @@ def cpu_fbank_baseline(n_utts, seconds, threads, min_wall):
     return frames / dt, frames, dt, passes
 
 
+DUMP_MAX_BYTES = 60_000_000  # per array; one array per workload, so at most 64 MB in all
+
+
+def dump_outputs(dirname, name, rows, rank=0):
+    """--dump-outputs: write the 2-D device tensor `rows` (what the last timed
+    step handed its caller) to dirname/<name>.npy as float32.  An array above
+    DUMP_MAX_BYTES is cut to a sample of its rows, drawn once with a fixed
+    seed from the row count alone and kept in row order, so two builds run
+    with the same arguments write the same rows."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n, row_bytes = rows.shape[0], 4 * rows.shape[1]
+    keep = DUMP_MAX_BYTES // row_bytes
+    if n > keep:
+        idx = np.sort(np.random.default_rng(20250117).choice(n, size=keep, replace=False))
+        rows = rows[torch.from_numpy(idx).to(rows.device)]
+    out = rows.detach().cpu().numpy().astype(np.float32, copy=False)  # (the copy waits for the device)
+    np.save(os.path.join(dirname, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), out)
+
+
 def main_c2(args):
     """BASELINE.json config C2: batched fbank (window + SRFFT + mel + log)
     over 1000 x 10 s synthetic utterances resident in HBM, one launch per
@@ -597,6 +631,8 @@ def main_c2(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     checksum = float(feats.double().sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "fbank", feats, rank)
     iv = []
     if not args.no_profile:
         iv = ctx.profile_intervals(ctx.PROF_FBANK)
@@ -625,7 +661,7 @@ def main_c2(args):
         if valu is not None:
             roofline["valu_counters"] = valu
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         threads, how = usable_cores()
         v, fr, dt, passes = cpu_fbank_baseline(max(64, 2 * threads), args.seconds, threads, args.cpu_seconds)
         cpu = {"value": round(v, 1), "unit": "frames/s", "cores": threads, "kind": "port",
@@ -843,6 +879,9 @@ def main_c4(args):
     for v in sums:
         checksum += v
     rows_in = gat.rows_in if gat is not None else 0
+    if args.dump_outputs and batches:
+        last = len(batches) - 1  # this rank's last batch of the pass
+        dump_outputs(args.dump_outputs, "loglik", outs[last % nbuf][:plans[last].total_frames], rank)
     busy = None
     n_gemm = 0
     stages = None
@@ -1301,6 +1340,11 @@ def main(argv=None):
     else:
         checksum += outs[(args.warmup + args.steps - 1) % nbuf].double().sum()
     finite = bool(torch.isfinite(outs[0]).all().item())
+    if args.dump_outputs:
+        # the last timed step this rank scored (rank 0 scores a share of the steps at N > 1)
+        mine = [i for i in range(args.warmup, args.warmup + args.steps) if scores(i)]
+        if mine:
+            dump_outputs(args.dump_outputs, "loglik", outs[mine[-1] % nbuf], rank)
     if dump is not None:
         arrs = {(f"r{seed_rank}s{k}" if isinstance(k, int) else f"r{seed_rank}{k}"): v.cpu().numpy()
                 for k, v in dump.items()}
@@ -1428,7 +1472,7 @@ def main(argv=None):
             stages["fbank"]["hbm_frac"] = round(stages["fbank"]["hbm_GBs"] / HBM_PEAK_GBS, 4)
 
     accuracy = None
-    if int8:
+    if int8 and args.full:
         # C5's question: how far do int8 posteriors move from fp32 (one batch)
         m32 = gpu.Model(ctx, conf)
         first = 0
@@ -1441,7 +1485,7 @@ def main(argv=None):
                     "argmax_agreement": float((a.argmax(1) == b.argmax(1)).double().mean().item())}
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         threads, how = usable_cores()
         n_cpu = max(args.cpu_utts, 2 * threads)
         v, fr, dt, passes = cpu_baseline(conf, n_cpu, args.seconds, threads, args.cpu_seconds)

@@ -136,3 +136,32 @@ def test_sink_share_default_balances_rank0_with_senders(bench):
         rank0 = 0.61 + 0.034 * (n - 1) - 0.71 * (1.0 - f)
         assert rank0 <= 0.67
     assert bench.sink_share_default(64) == 0.5
+
+
+def test_full_is_off_by_default(bench):
+    """A plain run does only what the headline figure needs: the CPU baseline
+    and the int8-against-fp32 leg wait for --full."""
+    assert bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"]).full is False
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d" and a.steps == 200
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(bench, tmp_path):
+    """--dump-outputs: a small array is written whole; one above the bound as
+    a sample of rows that depends on the row count alone (same rows from run
+    to run and from build to build), in row order, as float32."""
+    import numpy as np
+    import torch
+    small = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    bench.dump_outputs(str(tmp_path / "a"), "x", small)
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), small.numpy())
+    cols = 3456
+    n = bench.DUMP_MAX_BYTES // (4 * cols) + 1000
+    big = (torch.arange(n, dtype=torch.float32)[:, None] + torch.zeros(cols)).contiguous()
+    bench.dump_outputs(str(tmp_path / "a"), "y", big)
+    bench.dump_outputs(str(tmp_path / "b"), "y", big.clone(), rank=1)
+    y = np.load(tmp_path / "a" / "y.npy")
+    assert y.dtype == np.float32 and y.nbytes <= bench.DUMP_MAX_BYTES < 64e6
+    assert y.shape == (bench.DUMP_MAX_BYTES // (4 * cols), cols)
+    assert np.all(np.diff(y[:, 0]) > 0) and np.all(y[:, 0] == y[:, -1])
+    assert np.array_equal(y, np.load(tmp_path / "b" / "y.rank1.npy"))

@@ -269,3 +269,19 @@ def test_rehearse_peers_runs_and_reports():
     line = _bench_c3(["--rehearse-peers", "2"], 1)
     assert line["rehearse_peers"]["peers"] == 2 and line["finite"]
     assert line["config"]["frames_total"] == line["config"]["frames_per_step_per_gpu"] * 6
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: DIR/loglik.npy holds the rows of the last
+    timed step (step warmup + steps - 1 = 7 here), as float32, bit for bit
+    what --c3-dump kept of that step; a run without --full carries no CPU
+    baseline, and --steps is the number of timed steps."""
+    d = tmp_path / "out"
+    line = _bench_c3(["--fold-all", "--c3-dump", str(tmp_path / "all.npz"), "--dump-outputs", str(d)], 1)
+    assert line["steps"] == 6 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    assert sorted(os.listdir(d)) == ["loglik.npy"]
+    got, every = np.load(d / "loglik.npy"), np.load(tmp_path / "all.npz")
+    assert got.dtype == np.float32 and got.shape == (line["config"]["frames_per_step_per_gpu"], 512)
+    assert got.nbytes <= 64e6
+    assert np.array_equal(got.view(np.uint32), every["r0s7"].view(np.uint32))
+    assert not np.array_equal(got, every["r0s6"])  # (each step scores other utterances)

@@ -15,7 +15,7 @@ for W in "" _c2 _c5; do
   grep '^{' "$log" | tail -1 > "$P/${TAG}${W}_bench.json"
   cp "$prof/run_kernel_stats.csv" "$P/${TAG}${W}_kernel_stats.csv"
   python "$R/tools/trace_summary.py" "$prof/run_kernel_trace.csv" --window --check "$log" \
-    "rocprofv3 --kernel-trace --stats -- python bench.py ${W:+--workload ${W#_}}  (tools/round_gpu.sh, TAG=$TAG)
+    "rocprofv3 --kernel-trace --stats -- python bench.py --full ${W:+--workload ${W#_}}  (tools/round_gpu.sh, TAG=$TAG)
 bench JSON line of the same command: profiles/${TAG}${W}_bench.json
 " > "$P/${TAG}${W}_kernel_summary.txt"
   [ -f "$S/pmc_traffic${W}.json" ] && cp "$S/pmc_traffic${W}.json" "$P/${TAG}${W}_pmc_traffic.json"

@@ -6,7 +6,7 @@ OUT="$R/gpurun_out/$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python "$R/bench.py" --workload c2 --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS} > "$OUT/bench.log" 2>&1; rc=$?
+    python "$R/bench.py" --workload c2 --steps ${STEPS:-20} --warmup 3 --full ${BENCH_ARGS} > "$OUT/bench.log" 2>&1; rc=$?
 echo "c2 bench rc=$rc"; grep '^{' "$OUT/bench.log" | cut -c1-600
 [ $rc -eq 0 ] || { tail -20 "$OUT/bench.log"; exit $rc; }
 [ -n "$SKIP_PMC" ] && exit 0

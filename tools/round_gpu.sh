@@ -12,7 +12,7 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 [ -n "$SKIP_BENCH" ] && exit 0
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python "$R/bench.py" --steps ${STEPS:-50} --warmup 5 ${BENCH_ARGS} > "$OUT/bench.log" 2>&1; rc=$?
+    python "$R/bench.py" --steps ${STEPS:-50} --warmup 5 --full ${BENCH_ARGS} > "$OUT/bench.log" 2>&1; rc=$?
 echo "bench(rocprof) rc=$rc"; tail -2 "$OUT/bench.log"
 [ $rc -eq 0 ] || exit $rc
 [ -n "$SKIP_PMC" ] && exit 0
@@ -35,7 +35,7 @@ python "$R/tools/pmc_mfma.py" "$OUT/pmc3" "$OUT/pmc_mfma.json"
 # secondary workloads: C2 (batched fbank) and C5 (int8 nnet), same recipe
 for W in c2 c5; do
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$W" -o run -- \
-      python "$R/bench.py" --workload $W --steps ${STEPS_EXTRA:-30} --warmup 3 > "$OUT/bench_$W.log" 2>&1 || { echo "bench $W failed"; tail -20 "$OUT/bench_$W.log"; exit 1; }
+      python "$R/bench.py" --workload $W --steps ${STEPS_EXTRA:-30} --warmup 3 --full > "$OUT/bench_$W.log" 2>&1 || { echo "bench $W failed"; tail -20 "$OUT/bench_$W.log"; exit 1; }
   echo "bench $W ok"; grep '^{' "$OUT/bench_$W.log" | cut -c1-300
   case $W in c2) KRE="fbank";; c5) KRE="gemm_i8|quantize|minmax";; esac
   i=0
