@@ -36,10 +36,10 @@ HOSTFLAGS := -O2 -fPIC -std=c++17 -ffp-contract=off -Iinclude -I$(SRC) -I/opt/ro
              -D__HIP_PLATFORM_AMD__ -Wall $(EXPFLAGS)
 
 KERNELS := $(wildcard $(SRC)/kernels/*.hip)
-HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc
+HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
-        $(patsubst $(SRC)/%.cc,$(OBJ)/%.o,$(HOSTSRC))
-HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h
+        $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
+HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/cmvn_ops.h
 
 all: $(LIB) oracle
 
@@ -71,8 +71,10 @@ $(OBJ)/%.o: $(SRC)/kernels/%.hip $(HDRS) Makefile
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/%.o: $(SRC)/%.cc $(HDRS)
-	@mkdir -p $(OBJ)
+# host objects in a directory of their own: sessions.cc and
+# kernels/sessions.hip share a stem
+$(OBJ)/cc/%.o: $(SRC)/%.cc $(HDRS)
+	@mkdir -p $(OBJ)/cc
 	$(CXX) $(HOSTFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cctype>
 #include <fstream>
@@ -30,6 +31,11 @@ int hip_fail(hipError_t e, const char *what) {
 
 // ---------------------------------------------------------------- DevBuf --
 
+// ce_gpu_debug_counters
+static std::atomic<int64_t> g_device_allocs{0}, g_device_frees{0};
+void count_device_alloc() { g_device_allocs.fetch_add(1, std::memory_order_relaxed); }
+void count_device_free() { g_device_frees.fetch_add(1, std::memory_order_relaxed); }
+
 int DevBuf::alloc(size_t n) {
   release();
   if (n == 0) return CE_GPU_OK;
@@ -39,6 +45,7 @@ int DevBuf::alloc(size_t n) {
     (void)hipGetLastError();
     return fail(CE_GPU_ENOMEM, fmt("hipMalloc(%zu) failed: %s", n, hipGetErrorString(e)));
   }
+  count_device_alloc();
   bytes = n;
   return CE_GPU_OK;
 }
@@ -50,7 +57,10 @@ int DevBuf::upload(const void *src, size_t n) {
 }
 
 void DevBuf::release() {
-  if (ptr) (void)hipFree(ptr);
+  if (ptr) {
+    (void)hipFree(ptr);
+    count_device_free();
+  }
   ptr = nullptr;
   bytes = 0;
 }
@@ -419,8 +429,6 @@ static int ensure_lat_part(ce_gpu_ctx *ctx, size_t floats) {
   return ctx->lat_part.alloc(floats * sizeof(float));
 }
 
-int fbank_frames_per_block();
-
 static hipEvent_t pool_event(ce_gpu_ctx *ctx) {
   if (!ctx->event_pool.empty()) {
     hipEvent_t e = ctx->event_pool.back();
@@ -475,7 +483,7 @@ extern "C" {
 
 const char *ce_gpu_last_error(void) { return last_error(); }
 
-const char *ce_gpu_version(void) { return "catears-mi355x 0.5 (gfx950)"; }
+const char *ce_gpu_version(void) { return "catears-mi355x 0.6 (gfx950)"; }
 
 int ce_gpu_ctx_create(int device, void *stream, ce_gpu_ctx **out) {
   if (!out) return fail(CE_GPU_EINVAL, "out is NULL");
@@ -604,6 +612,12 @@ int ce_gpu_profile_anchor(int device, void *stream) {
   CE_HIP(hipSetDevice(device));
   if (!g_anchor[device]) CE_HIP(hipEventCreate(&g_anchor[device]));
   CE_HIP(hipEventRecord(g_anchor[device], static_cast<hipStream_t>(stream)));
+  return CE_GPU_OK;
+}
+
+int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees) {
+  if (device_allocs) *device_allocs = g_device_allocs.load(std::memory_order_relaxed);
+  if (device_frees) *device_frees = g_device_frees.load(std::memory_order_relaxed);
   return CE_GPU_OK;
 }
 
@@ -1418,6 +1432,54 @@ static int quantize_weights(ce_gpu_ctx *ctx, Step &st) {
   (void)ctx;
   return CE_GPU_OK;
 }
+
+int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats, int rows, const int *row_src,
+                      const uint32_t *row_edge, const int *row_dst, float *d_loglik) {
+  const float *y = nullptr;
+  int ldy = 0;
+  LatTail tail;
+  CE_TRY(run_steps(ctx, m, feats, m->input_dim, rows, row_src, row_edge, &y, &ldy,
+                   lat_tail_ok(d_loglik, m->log_prior.as<float>()) ? &tail : nullptr));
+  ProfScope prof(ctx, CE_GPU_PROF_FINALIZE);
+  return finalize_output(ctx, y, ldy, 0, rows, m->num_pdfs, m->final_log_softmax, m->log_prior.as<float>(), row_dst,
+                         d_loglik, tail);
+}
+
+// The sizes below are the ones run_steps_f32 / _x6f / _x6 / _x3 ask the
+// ensure_* calls for; the largest of them covers every mode the model can be
+// switched to later.
+int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows) {
+  if (m->int8) return fail(CE_GPU_ENOTSUP, "reserve_packed_rows: int8 model");
+  const size_t r = (size_t)rows;
+  size_t ws = 2 * r * m->max_width, scratch = 0, lat = 0;
+  int max_in = 0;
+  bool all_gemm = true;
+  for (const Step &st : m->steps) {
+    if (!st.is_gemm) {
+      all_gemm = false;
+      continue;
+    }
+    const GemmLayer &g = st.gemm;
+    max_in = std::max(max_in, std::max(g.kpad, (g.n + 63) / 64 * 64));
+    if (g.din % 32 != 0) scratch = std::max(scratch, r * g.kpad * sizeof(float));
+  }
+  if (m->x6_ok && all_gemm) {
+    // three bf16 planes (1.5 floats per element) cover the fp32 chain and
+    // the two fp16 planes as well
+    const size_t blk = (r * max_in * 3 / 2 + 1 + 63) / 64 * 64;
+    ws = std::max(ws, 2 * blk + r * m->num_pdfs);
+    for (size_t i = 0; i < m->steps.size(); ++i) {
+      const GemmLayer &g = m->steps[i].gemm;
+      const int kpad = i == 0 ? g.kpad : g.nseg * g.din;
+      if (kpad % 32 == 0) lat = std::max(lat, x6_lat_part_floats(rows, g.n, x6_lat_slices(kpad, g.n)));
+    }
+    CE_TRY(ensure_overflow_word(ctx));
+  }
+  CE_TRY(ensure_workspace(ctx, ws));
+  if (scratch) CE_TRY(ensure_scratch(ctx, scratch));
+  if (lat) CE_TRY(ensure_lat_part(ctx, lat));
+  return CE_GPU_OK;
+}
 }  // namespace catears
 
 extern "C" {
@@ -1433,17 +1495,9 @@ int ce_gpu_am_forward(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan 
   if (m->left != m->net_left || m->right != m->net_right)
     return fail(CE_GPU_EINVAL, "model context differs from its network's");
   for (const ce_gpu_plan::Chunk &c : p->chunks) {
-    const int *row_src = p->d_row_src.as<int>() + c.map_base;
-    const int *row_dst = p->d_row_dst.as<int>() + c.map_base;
-    const float *y = nullptr;
-    int ldy = 0;
-    const uint32_t *row_edge = p->d_row_edge.as<uint32_t>() + c.map_base;
-    LatTail tail;
-    CE_TRY(run_steps(ctx, m, d_feats, m->input_dim, c.rows, row_src, row_edge, &y, &ldy,
-                     lat_tail_ok(d_loglik, m->log_prior.as<float>()) ? &tail : nullptr));
-    ProfScope prof(ctx, CE_GPU_PROF_FINALIZE);
-    CE_TRY(finalize_output(ctx, y, ldy, 0, c.rows, m->num_pdfs, m->final_log_softmax, m->log_prior.as<float>(),
-                           row_dst, d_loglik, tail));
+    CE_TRY(score_packed_rows(ctx, m, d_feats, c.rows, p->d_row_src.as<int>() + c.map_base,
+                             p->d_row_edge.as<uint32_t>() + c.map_base, p->d_row_dst.as<int>() + c.map_base,
+                             d_loglik));
   }
   return CE_GPU_OK;
 }

@@ -73,6 +73,11 @@ struct DevBuf {
   T *as() const { return static_cast<T *>(ptr); }
 };
 
+// ce_gpu_debug_counters: every allocation / release that reaches the HIP
+// runtime (DevBuf, and the sessions' pinned buffers and events) counts once.
+void count_device_alloc();
+void count_device_free();
+
 // ------------------------------------------------------------ fbank tables --
 
 // Fixed fbank geometry (src/fbank.h:7-13).
@@ -341,6 +346,7 @@ struct ce_gpu_ctx {
   int wide_tiles = 0;          // ce_gpu_ctx_set_wide_tiles: 128 x 128 bf16x6 tiles (all CUs per launch)
   int fbank_mode = 0;          // ce_gpu_ctx_set_fbank: CE_GPU_FBANK_EXACT / _FAST
   std::vector<int32_t> h_blk_maps;
+  struct ce_gpu_sessions *sessions = nullptr;  // the context's session set (at most one)
   // optional per-class launch timing (ce_gpu_ctx_profile)
   bool profiling = false;
   unsigned prof_mask = ~0u;  // classes timed while profiling (ce_gpu_ctx_profile_classes)
@@ -427,6 +433,13 @@ int launch_fbank(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, 
                  float *feats, float *mel);
 int launch_fbank_s16(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, const int16_t *pcm,
                      float *feats, float *mel);
+// The same from a descriptor's three device arrays (no plan; the sessions
+// stage int16 input as float, so only the float form exists): utterance u
+// reads pcm + sample_off[u] and writes feats rows frame_off[u] ..
+// frame_off[u + 1] - 1; block_utt[b] = utterance of frame b * fbank_frames_per_block().
+int launch_fbank(hipStream_t s, const FbankTables *d_tab, const int64_t *d_sample_off, const int64_t *d_frame_off,
+                 const int *d_block_utt, int64_t total_frames, const float *pcm, float *feats, float *mel);
+int fbank_frames_per_block();
 // fast mode (ce_gpu_ctx_set_fbank(ctx, CE_GPU_FBANK_FAST))
 // the fast mode: fbank.hip's lane program with FMA contraction (fbank_fma.hip)
 #ifdef CATEARS_EXPERIMENTS  // kernels/fbank_nocase.hip: timing only
@@ -439,6 +452,8 @@ int launch_fbank_fma(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan 
                      float *mel);
 int launch_fbank_fma_s16(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, const int16_t *pcm,
                          float *feats, float *mel);
+int launch_fbank_fma(hipStream_t s, const FbankTables *d_tab, const int64_t *d_sample_off, const int64_t *d_frame_off,
+                     const int *d_block_utt, int64_t total_frames, const float *pcm, float *feats, float *mel);
 int launch_cmvn(hipStream_t s, const ce_gpu_plan *p, const float *gstats, const float *in,
                 float *out);
 
@@ -572,5 +587,45 @@ size_t i8_gemm_parts(int m, int n);
 int i8_k_align();
 int launch_gemm_u8_ws(hipStream_t s, int m, int n, int k, const uint8_t *a, const void *pa,
                       const uint8_t *b, const void *pb, float *c_f32, int32_t *c_i32, void *ws);
+
+// ---- device-resident sessions (sessions.cc, kernels/sessions.hip) ----
+
+// One chunk of packed rows through the nnet and the finalize (capi.cc, what
+// ce_gpu_am_forward runs per plan chunk): packed row r reads feature row
+// row_src[r] of feats (input_dim wide) and, when row_dst[r] >= 0, becomes row
+// row_dst[r] of d_loglik.
+int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats, int rows, const int *row_src,
+                      const uint32_t *row_edge, const int *row_dst, float *d_loglik);
+// Grows the context's nnet workspaces to what score_packed_rows needs for
+// `rows` packed rows in any GEMM mode and in latency mode, so that later
+// calls of up to that many rows allocate nothing.
+int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows);
+
+// One pushed slot of a session push (device image, written by the host).
+struct SessionPush {
+  int64_t pcm_off;   // first new sample in the caller's d_pcm
+  int32_t slot;
+  int32_t tail;      // samples carried in the slot's staging region
+  int32_t n_new;     // samples of this push
+  int32_t frames;    // frames the push completes
+  int32_t t0;        // index of the first of them in the slot's utterance
+  int32_t tmp_row;   // their first row in the linear fbank temporary
+};
+// Copies every push's new samples behind its slot's tail: staging region of
+// slot s at stage + s * stride floats.
+int launch_session_stage(hipStream_t s, const SessionPush *d_push, int n, int max_new, const float *pcm, float *stage,
+                         int64_t stride);
+int launch_session_stage_s16(hipStream_t s, const SessionPush *d_push, int n, int max_new, const int16_t *pcm,
+                             float *stage, int64_t stride);
+// Moves what the push's frames did not consume (tail + n_new - 160 * frames
+// samples, at most kWinLen - 1 once a frame exists) to the front of each region.
+int launch_session_carry(hipStream_t s, const SessionPush *d_push, int n, float *stage, int64_t stride);
+// Online CMVN resumed at frame t0 per pushed slot: appends the push's raw
+// frames (tmp) to the slot's raw ring (raw_cap rows), replays the chain from
+// the slot's carry (zero when t0 == 0) and writes the normalised frames to
+// the slot's ring of norm_cap rows.  gstats == NULL: copies tmp to the
+// normalised ring instead.
+int launch_session_cmvn(hipStream_t s, const SessionPush *d_push, int n, int total_frames, const float *gstats,
+                        const float *tmp, float *raw, int raw_cap, float *norm, int norm_cap, float *carry);
 
 }  // namespace catears

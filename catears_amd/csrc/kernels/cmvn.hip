@@ -12,13 +12,13 @@
 // the reference for any input.
 #include <hip/hip_runtime.h>
 
+#include "../cmvn_ops.h"
 #include "../internal.h"
 
 namespace catears {
 namespace {
 
-constexpr int kWindow = 600;  // PK_ONLINECMVN_WINDOW, src/cmvn.h:10
-constexpr int kGlobal = 200;  // PK_ONLINECMVN_GLOBALFRAMES, src/cmvn.h:11
+constexpr int kWindow = kCmvnWindow;
 
 #ifndef CMVN_TILE
 #define CMVN_TILE 48
@@ -27,35 +27,13 @@ constexpr int kGlobal = 200;  // PK_ONLINECMVN_GLOBALFRAMES, src/cmvn.h:11
 // batch's CMVN from 0.098 to 0.092 ms (tools/experiments/gpu_r5j.sh)
 constexpr int kTile = CMVN_TILE;
 
-// The chain of one (utterance, dimension) runs in three regimes of t:
-//   t <  599: SmoothStats adds alpha_t * [g, N_g] (count = t + 1 < 600);
-//   t == 599: count = 600, neither smoothing nor window subtraction;
-//   t >= 600: frame t - 600 leaves the window (no smoothing).
-// Each regime is its own loop, so no step carries a select, and the per-step
-// work is the reference's arithmetic only (the kernel is issue-bound: one
-// wave per utterance, a latency chain per lane).
-enum CmvnMode { kSmooth, kPlain, kWindowed };
+// The chain's three regimes of t (cmvn_ops.h: t < 599 smoothing, t == 599
+// plain, t >= 600 windowed) are each their own loop, so no step carries a
+// select, and the per-step work is the reference's arithmetic only (the
+// kernel is issue-bound: one wave per utterance, a latency chain per lane).
 
-template <int M>
-__device__ __forceinline__ float cmvn_step(float &carry, float c, float o, float al, float ng, float g) {
-  // ComputeStats (cmvn.cc:35-68): double temp seeded from the float carry
-  double acc = (double)carry;
-  acc += (double)c;
-  if (M == kWindowed) acc += -1.0 * (double)o;
-  carry = (float)acc;
-  // SmoothStats / Apply (cmvn.cc:80-88, 91-98) are AddVec calls, whose
-  // alpha == 1 branch (vector.cc:249-256) adds v instead of 1 * v: the same
-  // float, so no select here
-  float s = carry;
-  if (M == kSmooth) s = s + al * g;
-  return c + ng * s;
-}
-
-// Everything in SmoothStats/Apply except the per-dimension sums depends only
-// on the frame index t (count = min(t+1, 600)) and on N_g, so it is computed
-// once per block into LDS: alpha_t (the float scalar of AddVec, cmvn.cc:80-88)
-// and neg_t = -(float)(1 / smoothed count) (cmvn.cc:93-97).  For t >= 599 no
-// smoothing happens and the count is exactly 600.
+// The per-frame-index tables (alpha_t, -1 / count_t) are computed once per
+// block into LDS (cmvn_fill_tables).
 __global__ __launch_bounds__(64) void cmvn_kernel(const int64_t *__restrict__ frame_off,
                                                   const float *__restrict__ gstats,
                                                   const float *__restrict__ in,
@@ -63,18 +41,7 @@ __global__ __launch_bounds__(64) void cmvn_kernel(const int64_t *__restrict__ fr
   __shared__ float s_alpha[kWindow], s_neg[kWindow + 1];
   const int u = blockIdx.x, d = threadIdx.x;
   const float g_count = gstats[kMel];
-  for (int t = d; t <= kWindow; t += 64) {
-    float count = (float)(t + 1 < kWindow ? t + 1 : kWindow);
-    float alpha = 0.0f;
-    if ((double)count < kWindow) {  // SmoothStats (cmvn.cc:70-89)
-      double from_global = kWindow - (double)count;
-      if (from_global > kGlobal) from_global = kGlobal;
-      alpha = (float)(from_global / (double)g_count);
-      count = alpha != 1.0f ? count + alpha * g_count : count + g_count;
-    }
-    if (t < kWindow) s_alpha[t] = alpha;
-    s_neg[t] = -(float)(1 / (double)count);  // Apply (cmvn.cc:91-98)
-  }
+  cmvn_fill_tables(s_alpha, s_neg, g_count, d);
   __syncthreads();
   if (d >= kMel) return;
   const int64_t r0 = frame_off[u];

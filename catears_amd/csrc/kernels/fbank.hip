@@ -187,35 +187,45 @@ __global__ __launch_bounds__(kWaves * 64, 4) void FB8_KERNEL(const FbankTables *
   }
 }
 
+// The launch from the three device arrays of a descriptor (a plan's, or the
+// one a session set rewrites per push): utterance u's samples start at
+// pcm + sample_off[u], its frames are rows frame_off[u] .. frame_off[u + 1] - 1
+// of feats, block_utt[b] is the utterance of frame b * kFramesPerBlock.
 template <typename Sample>
-int launch_fbank_t(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, const Sample *pcm, float *feats,
-                   float *mel) {
-  if (p->total_frames == 0) return CE_GPU_OK;
-  const int64_t per_block = kWaves * kLanes, blocks = (p->total_frames + per_block - 1) / per_block;
+int launch_fbank_t(hipStream_t s, const FbankTables *d_tab, const int64_t *d_sample_off, const int64_t *d_frame_off,
+                   const int *d_block_utt, int64_t total_frames, const Sample *pcm, float *feats, float *mel) {
+  if (total_frames == 0) return CE_GPU_OK;
+  const int64_t per_block = kWaves * kLanes, blocks = (total_frames + per_block - 1) / per_block;
   const int64_t max_blocks = 256 * kBlocksPerCU;
   const unsigned grid = (unsigned)(blocks < max_blocks ? blocks : max_blocks);
   if (mel)
-    hipLaunchKernelGGL((FB8_KERNEL<Sample, true>), dim3(grid), dim3(kWaves * 64), 0, s, d_tab, pcm,
-                     p->d_sample_off.as<int64_t>(), p->d_frame_off.as<int64_t>(),
-                     p->d_block_utt.as<int>(), p->total_frames, feats, mel);
-    else
-    hipLaunchKernelGGL((FB8_KERNEL<Sample, false>), dim3(grid), dim3(kWaves * 64), 0, s, d_tab, pcm,
-                     p->d_sample_off.as<int64_t>(), p->d_frame_off.as<int64_t>(),
-                     p->d_block_utt.as<int>(), p->total_frames, feats, mel);
+    hipLaunchKernelGGL((FB8_KERNEL<Sample, true>), dim3(grid), dim3(kWaves * 64), 0, s, d_tab, pcm, d_sample_off,
+                       d_frame_off, d_block_utt, total_frames, feats, mel);
+  else
+    hipLaunchKernelGGL((FB8_KERNEL<Sample, false>), dim3(grid), dim3(kWaves * 64), 0, s, d_tab, pcm, d_sample_off,
+                       d_frame_off, d_block_utt, total_frames, feats, mel);
   CE_HIP(hipGetLastError());
   return CE_GPU_OK;
 }
 
 }  // namespace
 
+int FB8_LAUNCH(hipStream_t s, const FbankTables *d_tab, const int64_t *d_sample_off, const int64_t *d_frame_off,
+               const int *d_block_utt, int64_t total_frames, const float *pcm, float *feats, float *mel) {
+  return launch_fbank_t(s, d_tab, d_sample_off, d_frame_off, d_block_utt, total_frames, pcm, feats, mel);
+}
+
+// the plan's descriptor
 int FB8_LAUNCH(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, const float *pcm, float *feats,
                float *mel) {
-  return launch_fbank_t(s, d_tab, p, pcm, feats, mel);
+  return launch_fbank_t(s, d_tab, p->d_sample_off.as<int64_t>(), p->d_frame_off.as<int64_t>(),
+                        p->d_block_utt.as<int>(), p->total_frames, pcm, feats, mel);
 }
 
 int FB8_LAUNCH_S16(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, const int16_t *pcm,
                    float *feats, float *mel) {
-  return launch_fbank_t(s, d_tab, p, pcm, feats, mel);
+  return launch_fbank_t(s, d_tab, p->d_sample_off.as<int64_t>(), p->d_frame_off.as<int64_t>(),
+                        p->d_block_utt.as<int>(), p->total_frames, pcm, feats, mel);
 }
 
 #if !defined(FB8_FMA) && !defined(FB8_NOCASE)

@@ -33,6 +33,8 @@ ABI = [
     "ce_gpu_model_set_gemm", "ce_gpu_model_get_gemm", "ce_gpu_ctx_overflow", "ce_gpu_ctx_set_latency",
     "ce_gpu_fbank_s16", "ce_gpu_score_s16", "ce_gpu_ctx_set_fbank", "ce_gpu_sum_f64", "ce_gpu_ctx_set_wide_tiles",
     "ce_gpu_sum_f64_many", "ce_gpu_trace_mark", "ce_gpu_nnet_check_mem",
+    "ce_gpu_sessions_create", "ce_gpu_sessions_destroy", "ce_gpu_sessions_reset", "ce_gpu_sessions_push",
+    "ce_gpu_sessions_push_s16", "ce_gpu_debug_counters",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -58,6 +60,7 @@ def lib():
     vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     pp = ctypes.POINTER(ctypes.c_void_p)
     pi, pi64 = ctypes.POINTER(ci), ctypes.POINTER(i64)
+    pi32 = ctypes.POINTER(ctypes.c_int32)
     sig = {
         "ce_gpu_last_error": (ctypes.c_char_p, []),
         "ce_gpu_version": (ctypes.c_char_p, []),
@@ -109,6 +112,12 @@ def lib():
         "ce_gpu_ctx_set_wide_tiles": (ci, [vp, ci]),
         "ce_gpu_sum_f64": (ci, [vp, vp, i64, vp, vp]),
         "ce_gpu_sum_f64_many": (ci, [vp, ci, ctypes.POINTER(vp), pi64, vp, vp]),
+        "ce_gpu_debug_counters": (ci, [pi64, pi64]),
+        "ce_gpu_sessions_create": (ci, [vp, vp, vp, ci, ci, pp]),
+        "ce_gpu_sessions_destroy": (ci, [vp]),
+        "ce_gpu_sessions_reset": (ci, [vp, ci]),
+        "ce_gpu_sessions_push": (ci, [vp, ci, pi32, pi32, pi32, vp, vp, i64, pi32]),
+        "ce_gpu_sessions_push_s16": (ci, [vp, ci, pi32, pi32, pi32, vp, vp, i64, pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -394,6 +403,115 @@ def score(ctx, model, plan, pcm, global_stats=None, ws=None, out=None):
     fn = lib().ce_gpu_score_s16 if pcm.dtype == torch.int16 else lib().ce_gpu_score
     check(fn(ctx.h, model.h, plan.h, _ptr(pcm), _ptr(global_stats), _ptr(ws), _ptr(out)))
     return out
+
+
+SESSION_EOS = 1  # CE_GPU_SESSION_EOS
+
+
+def debug_counters():
+    """ce_gpu_debug_counters: (device allocations, device releases) the
+    library has made in this process so far."""
+    a, f = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().ce_gpu_debug_counters(ctypes.byref(a), ctypes.byref(f)))
+    return a.value, f.value
+
+
+class Sessions:
+    """ce_gpu_sessions: `n_slots` live audio streams scored incrementally,
+    their state (sample tail, CMVN sums and window, nnet context) on the
+    device.  `global_stats`: the 41-float device tensor of ce_gpu_cmvn, or
+    None for no CMVN.  One per context."""
+
+    def __init__(self, ctx, model, n_slots, max_chunk_samples, global_stats=None):
+        self.ctx, self.model = ctx, model
+        self.n_slots, self.max_chunk_samples = int(n_slots), int(max_chunk_samples)
+        self._gstats = global_stats  # the library keeps the pointer
+        self._state = [(0, 0, False)] * self.n_slots  # (samples, rows emitted, ended) per slot
+        h = ctypes.c_void_p()
+        check(lib().ce_gpu_sessions_create(ctx.h, model.h, _ptr(global_stats), self.n_slots,
+                                           self.max_chunk_samples, ctypes.byref(h)))
+        self.h = h
+
+    @staticmethod
+    def _advance(right, samples, rows, count, eos):
+        """One push of `count` samples to a slot that has `samples` samples
+        and `rows` emitted rows: (samples, frames completed, rows emitted,
+        rows total) after it."""
+        before = 0 if samples < 400 else 1 + (samples - 400) // 160
+        samples += count
+        frames = 0 if samples < 400 else 1 + (samples - 400) // 160
+        total = frames if eos else max(0, frames - right)
+        return samples, frames - before, total - rows, total
+
+    @staticmethod
+    def schedule(L, R, sample_counts, eos_at):
+        """What a slot's pushes produce: ([frames completed by push i],
+        [rows emitted by push i]) for pushes of sample_counts[i] samples, the
+        push of index `eos_at` (None: none) carrying the end of the
+        utterance.  A push emits every row whose R rows of right context
+        exist (all remaining rows at the end); the left context L delays
+        nothing (it clamps to frame 0).  Pure arithmetic, no device."""
+        samples = rows = 0
+        frames_out, rows_out = [], []
+        for i, c in enumerate(sample_counts):
+            if eos_at is not None and i > eos_at:
+                raise ValueError("push after the end of the utterance")
+            samples, f, r, rows = Sessions._advance(R, samples, rows, int(c), eos_at is not None and i == eos_at)
+            frames_out.append(f)
+            rows_out.append(r)
+        return frames_out, rows_out
+
+    def push(self, slots, pcm, counts, eos=None, out=None):
+        """Advance `slots` (distinct) by counts[i] new samples each, laid back
+        to back in the device tensor `pcm` (float32 at raw int16 scale, or
+        int16); eos[i] true ends slot i's utterance.  Returns (loglik, rows):
+        the newly complete rows of push 0, then push 1, ... and the row
+        count of each push.  `out`: a (>= rows, num_pdfs) device tensor to
+        write into (a view of its first rows is returned)."""
+        import torch
+        n = len(slots)
+        sl = np.ascontiguousarray(slots, np.int32)
+        cn = np.ascontiguousarray(counts, np.int32)
+        fl = np.zeros(n, np.int32) if eos is None else np.ascontiguousarray(
+            [SESSION_EOS if e else 0 for e in eos], np.int32)
+        assert len(cn) == n and len(fl) == n
+        after, need = {}, 0
+        for i in range(n):
+            k = int(sl[i])
+            if 0 <= k < self.n_slots and not self._state[k][2] and k not in after:
+                s, _, r, total = self._advance(self.model.right, self._state[k][0], self._state[k][1], int(cn[i]),
+                                               bool(fl[i]))
+                after[k] = (s, total, bool(fl[i]))
+                need += r
+        if pcm is not None and pcm.dtype not in (torch.int16, torch.float32):
+            raise TypeError("pcm must be float32 or int16")
+        dev = pcm.device if pcm is not None else torch.device("cuda", self.ctx.device)
+        if out is None:
+            out = torch.empty((max(need, 1), self.model.num_pdfs), dtype=torch.float32, device=dev)
+        rows = np.zeros(n, np.int32)
+        fn = lib().ce_gpu_sessions_push_s16 if pcm is not None and pcm.dtype == torch.int16 else lib().ce_gpu_sessions_push
+        p32 = ctypes.POINTER(ctypes.c_int32)
+        check(fn(self.h, n, sl.ctypes.data_as(p32), cn.ctypes.data_as(p32), fl.ctypes.data_as(p32), _ptr(pcm),
+                 _ptr(out), out.shape[0], rows.ctypes.data_as(p32)))
+        for k, st in after.items():
+            self._state[k] = st
+        return out[:int(rows.sum())], rows
+
+    def reset(self, slot):
+        """The slot starts a new utterance."""
+        check(lib().ce_gpu_sessions_reset(self.h, int(slot)))
+        self._state[int(slot)] = (0, 0, False)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ce_gpu_sessions_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def nnet_propagate(ctx, model, x, subtract_prior=False, out=None):

@@ -52,6 +52,7 @@ extern "C" {
 typedef struct ce_gpu_ctx ce_gpu_ctx;     /* device + stream + workspaces + fbank tables */
 typedef struct ce_gpu_model ce_gpu_model; /* device-resident nnet, log prior, contexts   */
 typedef struct ce_gpu_plan ce_gpu_plan;   /* geometry of one batch of utterances         */
+typedef struct ce_gpu_sessions ce_gpu_sessions; /* n_slots live audio streams, state in HBM */
 
 /* Message of the last failure on this thread ("" if none). */
 const char *ce_gpu_last_error(void);
@@ -60,7 +61,10 @@ const char *ce_gpu_last_error(void);
  * (INTEGRATION.md §5): 0.1 round 1; 0.2 ce_gpu_loglik_gather gained `dim`
  * (argument 5) -- a caller built against 0.1 must be rebuilt; 0.3 adds the
  * int16 PCM entry points (ce_gpu_fbank_s16, ce_gpu_score_s16) and the fast
- * fbank mode (ce_gpu_ctx_set_fbank). */
+ * fbank mode (ce_gpu_ctx_set_fbank); 0.4 ce_gpu_sum_f64(_many) and
+ * ce_gpu_ctx_set_wide_tiles; 0.5 no environment switch in the product
+ * library; 0.6 adds the device-resident sessions (ce_gpu_sessions_*) and
+ * ce_gpu_debug_counters. */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -172,6 +176,14 @@ int ce_gpu_ctx_profile_intervals(ce_gpu_ctx *ctx, int kernel_class, double *h_st
  * the launches between the two.  Measurement plumbing; no reference
  * counterpart. */
 int ce_gpu_trace_mark(int device, void *stream, int tag);
+
+/* Process-wide counts of the device allocations and releases the library has
+ * made so far: every hipMalloc / hipFree behind its buffers, and the pinned
+ * host buffers and events of a session set.  A serving loop (or a test)
+ * reads them before and after a stretch of calls to show that the stretch
+ * allocated nothing.  Either pointer may be NULL.  Measurement plumbing; no
+ * reference counterpart. */
+int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees);
 
 /* -------------------------------------------------------------- model --- */
 
@@ -351,6 +363,62 @@ int ce_gpu_score(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan *p,
 /* ce_gpu_score from 16-bit PCM (ce_gpu_fbank_s16 as its first stage). */
 int ce_gpu_score_s16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan *p, const int16_t *d_pcm,
                      const float *d_global_stats, float *d_feats_ws, float *d_loglik);
+
+/* ----------------------------------------------------------- sessions --- */
+/* Live audio that arrives in pieces, scored incrementally: the reference's
+ * own contract (ce_stt_process feeds Fbank::Process per read, src/fbank.cc:
+ * 265-314; CMVN::GetFrame src/cmvn.cc:100-119; AcousticModel::Process per
+ * frame, src/am.cc:115-142) for n_slots concurrent streams at once, with
+ * every stream's state in HBM: the unconsumed sample tail (at most 399
+ * samples), the CMVN running sums and its 600-frame window, and the nnet's
+ * left context.  ("Session", because "stream" means a HIP stream here.)
+ *
+ * Let a slot have received samples x[0..S) since its last reset and F =
+ * ce_gpu_fbank_num_frames(S).  After any sequence of pushes ending with
+ * CE_GPU_SESSION_EOS the rows the slot produced, concatenated, are
+ * bit-identical to the F rows ce_gpu_score / ce_gpu_score_s16 give for the
+ * one-utterance plan of x on the same context (same GEMM mode, latency and
+ * fbank settings, same d_global_stats or none).  Before EOS a push emits
+ * every row whose right context is complete: max(0, F - R) rows in total so
+ * far.  Which other slots share a push, and in which order, changes no bit.
+ * The host knows every count by arithmetic and never reads device state.
+ *
+ * A push allocates, frees and synchronizes nothing: its descriptors travel
+ * through a ring of pinned buffers with one asynchronous copy, and
+ * ce_gpu_sessions_create reserves every workspace (bounded by 4096 packed
+ * nnet rows per launch sequence, whatever n_slots x max_chunk_samples is).
+ *
+ * int8 models: CE_GPU_ENOTSUP (their rows depend on the batch).  A model
+ * whose input is not 40-dim fbank or that has no prior: CE_GPU_EINVAL.  One
+ * session set per context; calls on it are not thread-safe. */
+
+/* d_global_stats: 41 floats (device, must outlive the set), NULL = no CMVN.
+ * max_chunk_samples: the most samples one slot may receive in one push. */
+int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *d_global_stats,
+                           int n_slots, int max_chunk_samples, ce_gpu_sessions **out);
+/* Waits for the pushes in flight, then frees the set.  Destroy it before its
+ * context and its model. */
+int ce_gpu_sessions_destroy(ce_gpu_sessions *s);
+/* Slot starts a new utterance (ordered on the context's stream, no host block). */
+int ce_gpu_sessions_reset(ce_gpu_sessions *s, int slot);
+
+#define CE_GPU_SESSION_EOS 1   /* flag: this push ends the slot's utterance */
+/* Advance n distinct slots.  Push i gives slot h_slot[i] h_num_samples[i]
+ * (>= 0) new samples, laid back to back in d_pcm in push order (float at raw
+ * int16 scale, as ce_gpu_fbank).  h_flags may be NULL (no flags).  d_loglik
+ * receives the newly complete log-likelihood rows of push 0, then push 1, ...
+ * (num_pdfs floats each); h_rows_out[i] = rows push i produced.  If
+ * capacity_rows is too small: CE_GPU_EINVAL, h_rows_out still filled with the
+ * needed counts, no state changed, nothing enqueued.  EOS with F == 0 yields
+ * no rows; after EOS the slot accepts nothing until it is reset
+ * (CE_GPU_EINVAL). */
+int ce_gpu_sessions_push(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_num_samples,
+                         const int32_t *h_flags, const float *d_pcm, float *d_loglik,
+                         int64_t capacity_rows, int32_t *h_rows_out);
+/* The same from 16-bit PCM (as ce_gpu_fbank_s16): the same bits. */
+int ce_gpu_sessions_push_s16(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_num_samples,
+                             const int32_t *h_flags, const int16_t *d_pcm, float *d_loglik,
+                             int64_t capacity_rows, int32_t *h_rows_out);
 
 /* ------------------------------------------------------- linear algebra --- */
 
