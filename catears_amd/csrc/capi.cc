@@ -483,7 +483,7 @@ extern "C" {
 
 const char *ce_gpu_last_error(void) { return last_error(); }
 
-const char *ce_gpu_version(void) { return "catears-mi355x 0.6 (gfx950)"; }
+const char *ce_gpu_version(void) { return "catears-mi355x 0.7 (gfx950)"; }
 
 int ce_gpu_ctx_create(int device, void *stream, ce_gpu_ctx **out) {
   if (!out) return fail(CE_GPU_EINVAL, "out is NULL");
@@ -903,11 +903,27 @@ static bool splice_first_layer() {
   return on;
 }
 
+// ce_gpu_model_calibrate's tap: before each Linear runs, the (min, max) of
+// its input block (held rows only) is folded into ranges[2 * linear ..].
+struct CalibTap {
+  float *ranges = nullptr;  // device, 2 per Linear
+  void *part = nullptr;     // minmax partials (i8_params_scratch_bytes)
+  const uint32_t *row_edge = nullptr;
+  int linear = 0;
+};
+
+static int tap_input(ce_gpu_ctx *ctx, CalibTap *tap, const GemmLayer &g, const float *x, int ldx, int rows,
+                     const int *row_map) {
+  if (!tap) return CE_GPU_OK;
+  return launch_i8_range(ctx->stream, x, ldx, rows, g.din, row_map, tap->row_edge, g.in_left, g.in_right, tap->part,
+                         tap->ranges + 2 * tap->linear++);
+}
+
 // Runs the program's steps on `rows` packed rows starting at x (row_map: the
 // first layer's packed row -> source row, or NULL for identity).  Returns the
 // last activation via *y / *ldy.
 static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                         const int *row_map, const float **y, int *ldy) {
+                         const int *row_map, const float **y, int *ldy, CalibTap *tap = nullptr) {
   const size_t per = (size_t)rows * m->max_width;
   CE_TRY(ensure_workspace(ctx, 2 * per));
   float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
@@ -936,6 +952,7 @@ static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
       a.npost = g.npost;
       a.y = buf[cur];
       a.ldy = g.n;
+      CE_TRY(tap_input(ctx, tap, g, x, ldx, rows, a.row_map));
       {
         ProfScope prof(ctx, g.din % 32 == 0 ? CE_GPU_PROF_GEMM : CE_GPU_PROF_GEMM_GATHER);
         if (g.din % 32 != 0 && splice_first_layer()) {
@@ -1014,7 +1031,7 @@ static bool lat_fused_final() {
 }
 
 static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                         const int *row_map, const float **y, int *ldy, LatTail *tail) {
+                         const int *row_map, const float **y, int *ldy, LatTail *tail, CalibTap *tap = nullptr) {
   int max_in = 0;
   for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
   for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
@@ -1038,6 +1055,9 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
     const GemmLayer &g = m->steps[i].gemm;
     const bool last = i + 1 == m->steps.size();
     X6Gemm a;
+    // calibration: the block entering this layer's Splice (the caller's rows,
+    // or the previous layer's fp32 output)
+    CE_TRY(i == 0 ? tap_input(ctx, tap, g, x, ldx, rows, row_map) : tap_input(ctx, tap, g, xs, px, rows, nullptr));
     // the latency kernel and the default direct-weight kernel splice the
     // caller's rows themselves (din % 8 == 0): no splice_pad launch
     const bool lat_direct = i == 0 && g.din % 8 == 0 && ldx % 4 == 0 &&
@@ -1341,10 +1361,91 @@ static int run_steps_i8(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, 
   return CE_GPU_OK;
 }
 
+// Scratch of the static int8 program for `rows` rows: two operand buffers
+// (a GEMM with the requantize epilogue reads one and writes the other) and
+// three row-sum buffers (read / added into / cleared for the next launch).
+static void i8_static_scratch(const ce_gpu_model *m, int rows, size_t *q_bytes, size_t *rs_bytes) {
+  int max_ldq = 16;
+  for (const Step &st : m->steps)
+    if (st.is_gemm) max_ldq = std::max(max_ldq, st.i8.spliced ? st.i8.kpad : st.i8.in_width);
+  *q_bytes = ((size_t)rows * max_ldq + 255) / 256 * 256;
+  *rs_bytes = ((size_t)rows * 4 + 255) / 256 * 256;
+}
+
+// The static int8 program (ce_gpu_model_quantize_static): every Linear's
+// activation parameters are the model's frozen ones, so nothing is reduced
+// over the block.  A GEMM whose output is the next Linear's plain operand
+// (that layer reads whole 128-byte K-tiles of it) writes that layer's bytes
+// and row sums itself (I8NextBytes); every other layer input goes through the
+// quantize pass with the frozen parameters.  CATEARS_I8_FUSED=0 (experiments
+// library, read per call: tools/i8_static.py) keeps the quantize pass
+// everywhere.
+static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
+                               const int *row_map, const float **y, int *ldy) {
+  const size_t per = (size_t)rows * m->max_width;
+  CE_TRY(ensure_workspace(ctx, 2 * per));
+  float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
+  size_t q_bytes = 0, rs_bytes = 0;
+  i8_static_scratch(m, rows, &q_bytes, &rs_bytes);
+  CE_TRY(ensure_scratch(ctx, 2 * q_bytes + 3 * rs_bytes));
+  char *base = static_cast<char *>(ctx->scratch.ptr);
+  int8_t *xq[2] = {reinterpret_cast<int8_t *>(base), reinterpret_cast<int8_t *>(base + q_bytes)};
+  int32_t *rs[3];
+  for (int i = 0; i < 3; ++i) rs[i] = reinterpret_cast<int32_t *>(base + 2 * q_bytes + i * rs_bytes);
+  const bool fused_ok = CE_KNOB("CATEARS_I8_FUSED", 1) != 0;
+  int cur = 0, qc = 0, rc = 0;
+  bool first = true, have_bytes = false;  // have_bytes: the previous GEMM wrote xq[qc] / rs[rc]
+  for (size_t si = 0; si < m->steps.size(); ++si) {
+    const Step &st = m->steps[si];
+    if (!st.is_gemm) {
+      CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
+      continue;
+    }
+    const I8Layer &L = st.i8;
+    const int ldq = L.spliced ? L.kpad : L.in_width;
+    if (!have_bytes) {
+      ProfScope prof(ctx, CE_GPU_PROF_QUANT);
+      const int zero[1] = {0};
+      CE_TRY(launch_i8_quantize(ctx->stream, x, ldx, rows, L.in_width, first ? row_map : nullptr,
+                                L.spliced ? st.gemm.nseg : 1, L.spliced ? st.gemm.off : zero, L.qp, xq[qc], ldq, rs[rc],
+                                rs[(rc + 1) % 3]));
+    }
+    const I8Layer *N = si + 1 < m->steps.size() && m->steps[si + 1].is_gemm ? &m->steps[si + 1].i8 : nullptr;
+    const bool fuse = fused_ok && N && N->in_width == L.n && !N->spliced && i8_gemm_can_requantize(L, ldq);
+    ProfScope prof(ctx, CE_GPU_PROF_GEMM);
+    if (fuse) {
+      const I8NextBytes nb = {xq[qc ^ 1], rs[(rc + 1) % 3], rs[(rc + 2) % 3], N->qp};
+      CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, nullptr, nullptr, &nb));
+      qc ^= 1;
+      rc = (rc + 1) % 3;
+      x = nullptr;
+    } else {
+      CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n));
+      x = buf[cur];
+      cur ^= 1;
+    }
+    ldx = L.n;
+    have_bytes = fuse;
+    first = false;
+  }
+  *y = x;
+  *ldy = ldx;
+  return CE_GPU_OK;
+}
+
 static int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
                      const int *row_map, const uint32_t *row_edge, const float **y, int *ldy,
-                     LatTail *tail = nullptr) {
+                     LatTail *tail = nullptr, CalibTap *tap = nullptr) {
   if (tail) tail->active = false;
+  if (tap) {
+    // calibration reads fp32 activations between the layers
+    if (m->int8) return fail(CE_GPU_EINVAL, "model_calibrate: the model is already quantized");
+    if (m->gemm == CE_GPU_GEMM_BF16X6 && x6_f32in() && x6_plane_chain_env() == 0)
+      return run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, nullptr, tap);
+    if (m->gemm == CE_GPU_GEMM_FP32) return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy, tap);
+    return fail(CE_GPU_ENOTSUP, "model_calibrate: GEMM modes fp32 and bf16x6 only (the others keep activations as planes)");
+  }
+  if (m->int8 && m->int8_static) return run_steps_i8_static(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->int8) return run_steps_i8(ctx, m, x, ldx, rows, row_map, row_edge, y, ldy);
   if (m->gemm == CE_GPU_GEMM_F16X3) return run_steps_x3(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->gemm == CE_GPU_GEMM_BF16X6_PLANES) return run_steps_x6(ctx, m, x, ldx, rows, row_map, y, ldy);
@@ -1449,7 +1550,14 @@ int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats
 // ensure_* calls for; the largest of them covers every mode the model can be
 // switched to later.
 int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows) {
-  if (m->int8) return fail(CE_GPU_ENOTSUP, "reserve_packed_rows: int8 model");
+  if (m->int8 && !m->int8_static) return fail(CE_GPU_ENOTSUP, "reserve_packed_rows: int8 model");
+  if (m->int8_static) {
+    // what run_steps_i8_static asks for
+    size_t q_bytes = 0, rs_bytes = 0;
+    i8_static_scratch(m, rows, &q_bytes, &rs_bytes);
+    CE_TRY(ensure_workspace(ctx, 2 * (size_t)rows * m->max_width));
+    return ensure_scratch(ctx, 2 * q_bytes + 3 * rs_bytes);
+  }
   const size_t r = (size_t)rows;
   size_t ws = 2 * r * m->max_width, scratch = 0, lat = 0;
   int max_in = 0;
@@ -1540,12 +1648,13 @@ int ce_gpu_nnet_propagate(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *d
                                    m->net_left, m->net_right));
   if (subtract_prior && !m->log_prior.ptr) return fail(CE_GPU_EINVAL, "model has no prior");
   const int ctx_rows = m->net_left + m->net_right;
-  if (!m->int8 && rows > kPropagateWindow) {
+  if ((!m->int8 || m->int8_static) && rows > kPropagateWindow) {
     // A very long block (hours of audio in one call) runs as overlapping
     // windows: output row t needs input rows t .. t + L + R only, so the
     // windows give the same bits as one pass, keep every GEMM operand well
-    // inside the kernels' 32-bit row offsets and bound the workspace.  (An
-    // int8 model quantizes per call, so it keeps the single pass.)
+    // inside the kernels' 32-bit row offsets and bound the workspace.  (A
+    // dynamic int8 model quantizes per call, so it keeps the single pass; a
+    // static one has frozen parameters and is windowed like fp32.)
     const int step = kPropagateWindow - ctx_rows;
     for (int o = 0; o < out_rows; o += step) {
       const int n = std::min(step, out_rows - o);
@@ -1578,7 +1687,7 @@ int ce_gpu_nnet_propagate_blocks(ce_gpu_ctx *ctx, const ce_gpu_model *m, const f
     total += h_rows[b];
   }
   if (total >= INT32_MAX / 2) return fail(CE_GPU_EINVAL, "too many rows");
-  if (m->int8) {
+  if (m->int8 && !m->int8_static) {
     // per-tensor activation parameters are reduced over the block being
     // scored: one block per call keeps each block's rows its own
     const float *in = d_in;
@@ -1790,11 +1899,106 @@ int ce_gpu_sum_f64_many(void *stream, int count, const float *const *d_x, const 
 
 int ce_gpu_model_quantize(ce_gpu_ctx *ctx, ce_gpu_model *m) {
   if (!ctx || !m) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->int8_static) return fail(CE_GPU_EINVAL, "model_quantize: the model is static int8");
   if (m->int8) return CE_GPU_OK;
   CE_HIP(hipSetDevice(ctx->device));
   for (Step &st : m->steps)
     if (st.is_gemm) CE_TRY(quantize_weights(ctx, st));
   m->int8 = true;
+  return CE_GPU_OK;
+}
+
+int ce_gpu_quant_params_from_range(float min, float max, float *scale, int32_t *zero_point) {
+  if (!scale || !zero_point) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (!std::isfinite(min) || !std::isfinite(max) || min > max)
+    return fail(CE_GPU_EINVAL, fmt("quant_params_from_range: bad range [%g, %g]", (double)min, (double)max));
+  if (max < FLT_MIN) max = FLT_MIN;                // FindMinMax seeds max with FLT_MIN (matrix.cc:331-345)
+  const float width = max - min;                   // float, as the reference subtracts
+  const double s = width / 255.0;                  // ComputeQuantizationParams (matrix.cc:348-362)
+  if (!(s > 0.0) || !std::isfinite(s) || !((float)s > 0.0f))
+    return fail(CE_GPU_EINVAL, fmt("quant_params_from_range: [%g, %g] has no positive finite scale", (double)min,
+                                   (double)max));
+  *zero_point = (int32_t)round(-min / s);
+  *scale = (float)s;
+  return CE_GPU_OK;
+}
+
+int ce_gpu_model_calibrate(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan *p, const float *d_feats,
+                           int accumulate, float *h_ranges) {
+  if (!ctx || !m || !p || !h_ranges) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->int8) return fail(CE_GPU_EINVAL, "model_calibrate: the model is already quantized");
+  if (!p->has_model || p->left != m->left || p->right != m->right)
+    return fail(CE_GPU_EINVAL, "plan was not built for this model's context");
+  if (m->left != m->net_left || m->right != m->net_right)
+    return fail(CE_GPU_EINVAL, "model context differs from its network's");
+  if (!p->chunks.empty() && !d_feats) return fail(CE_GPU_EINVAL, "NULL argument");
+  const int n = m->num_linear;
+  if (!accumulate)
+    for (int i = 0; i < n; ++i) h_ranges[2 * i] = FLT_MAX, h_ranges[2 * i + 1] = FLT_MIN;  // FindMinMax's seeds
+  if (p->chunks.empty()) return CE_GPU_OK;
+  CE_HIP(hipSetDevice(ctx->device));
+  const size_t r_bytes = ((size_t)n * 8 + 255) / 256 * 256;
+  DevBuf work;
+  CE_TRY(work.alloc(r_bytes + i8_params_scratch_bytes()));
+  CalibTap tap;
+  tap.ranges = work.as<float>();
+  tap.part = static_cast<char *>(work.ptr) + r_bytes;
+  CE_HIP(hipMemcpyAsync(tap.ranges, h_ranges, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  for (const ce_gpu_plan::Chunk &c : p->chunks) {
+    const float *y = nullptr;
+    int ldy = 0;
+    tap.linear = 0;
+    tap.row_edge = p->d_row_edge.as<uint32_t>() + c.map_base;
+    CE_TRY(run_steps(ctx, m, d_feats, m->input_dim, c.rows, p->d_row_src.as<int>() + c.map_base, tap.row_edge, &y,
+                     &ldy, nullptr, &tap));
+  }
+  CE_HIP(hipMemcpyAsync(h_ranges, tap.ranges, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  CE_HIP(hipStreamSynchronize(ctx->stream));
+  return CE_GPU_OK;
+}
+
+int ce_gpu_model_quantize_static(ce_gpu_ctx *ctx, ce_gpu_model *m, const float *h_ranges, int n_ranges) {
+  if (!ctx || !m || !h_ranges) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->int8) return fail(CE_GPU_EINVAL, "model_quantize_static: the model is already quantized");
+  if (n_ranges != m->num_linear)
+    return fail(CE_GPU_EINVAL, fmt("model_quantize_static: %d ranges for %d Linear layers", n_ranges, m->num_linear));
+  struct HostQP {
+    float scale;
+    int32_t zp;
+  };
+  std::vector<HostQP> qp(n_ranges);
+  for (int i = 0; i < n_ranges; ++i)
+    CE_TRY(ce_gpu_quant_params_from_range(h_ranges[2 * i], h_ranges[2 * i + 1], &qp[i].scale, &qp[i].zp));
+  CE_HIP(hipSetDevice(ctx->device));
+  DevBuf d_qp;
+  CE_TRY(d_qp.upload(qp.data(), qp.size() * sizeof(HostQP)));
+  for (Step &st : m->steps)
+    if (st.is_gemm) CE_TRY(quantize_weights(ctx, st));
+  // nothing below fails: the model changes only now
+  m->i8_qp = std::move(d_qp);
+  int i = 0;
+  m->qp_scale.clear();
+  m->qp_zp.clear();
+  for (Step &st : m->steps) {
+    if (!st.is_gemm) continue;
+    st.i8.qp = m->i8_qp.as<HostQP>() + i;
+    m->qp_scale.push_back(qp[i].scale);
+    m->qp_zp.push_back(qp[i].zp);
+    ++i;
+  }
+  m->int8 = true;
+  m->int8_static = true;
+  return CE_GPU_OK;
+}
+
+int ce_gpu_model_quant_params(const ce_gpu_model *m, float *h_scale, int32_t *h_zero_point, int capacity, int *count) {
+  if (!m || !count) return fail(CE_GPU_EINVAL, "NULL argument");
+  const int n = m->int8_static ? (int)m->qp_scale.size() : 0;
+  *count = n;
+  for (int i = 0; i < std::min(n, std::max(capacity, 0)); ++i) {
+    if (h_scale) h_scale[i] = m->qp_scale[i];
+    if (h_zero_point) h_zero_point[i] = m->qp_zp[i];
+  }
   return CE_GPU_OK;
 }
 

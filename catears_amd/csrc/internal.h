@@ -260,6 +260,9 @@ struct I8Layer {
   const float *bias = nullptr, *bn_scale = nullptr, *bn_offset = nullptr;
   int post[4] = {0, 0, 0, 0};
   int npost = 0;
+  // static int8 (ce_gpu_model_quantize_static): this layer's frozen
+  // activation parameters in device memory (a QP of ce_gpu_model::i8_qp)
+  const void *qp = nullptr;
 };
 
 enum RowOpKind : int { kRowRelu, kRowBatchNorm, kRowLogSoftmax, kRowSoftmax, kRowNormalize };
@@ -397,6 +400,13 @@ struct ce_gpu_model {
   int64_t num_params = 0;
   bool final_log_softmax = false;
   bool int8 = false;                 // Linear layers run as Quantize + u8 GEMM
+  // int8 with one frozen activation (scale, zero point) per Linear instead
+  // of the scored block's (ce_gpu_model_quantize_static): rows no longer
+  // depend on their batch
+  bool int8_static = false;
+  catears::DevBuf i8_qp;             // num_linear x {float scale; int32 zp}
+  std::vector<float> qp_scale;       // the same on the host (ce_gpu_model_quant_params)
+  std::vector<int32_t> qp_zp;
   int gemm = 0;                      // CE_GPU_GEMM_* for the fp32 program
   bool x6_ok = false;                // program shape the bf16x6 / f16x3 paths take
   bool x3_ok = false;                // ... and every weight fits the f16x3 planes
@@ -568,9 +578,16 @@ size_t gemm_u8_scratch_bytes(int m, int n, int k);
 // segment) are >= in_left / in_right.
 int launch_i8_params(hipStream_t s, const float *x, int ldx, int rows, int width, const int *row_map,
                      const uint32_t *row_edge, int in_left, int in_right, void *part, void *params);
+// Calibration: the same reduction folded into range[0] (min) and range[1]
+// (max) on the device, which keep what they held before (`part` as above).
+int launch_i8_range(hipStream_t s, const float *x, int ldx, int rows, int width, const int *row_map,
+                    const uint32_t *row_edge, int in_left, int in_right, void *part, float *range);
 size_t i8_params_scratch_bytes();
+// `zero` (static int8): rows int32 words the pass clears, the row sums a
+// fused-requantize GEMM will add into (I8NextBytes::rowsum).
 int launch_i8_quantize(hipStream_t s, const float *x, int ldx, int rows, int width, const int *row_map, int nseg,
-                       const int *offs, const void *params, int8_t *q, int ldq, int32_t *rowsum);
+                       const int *offs, const void *params, int8_t *q, int ldq, int32_t *rowsum,
+                       int32_t *zero = nullptr);
 // The next layer's min / max, fused into this GEMM's epilogue: one float2
 // per wave into `part` (at least i8_gemm_parts(m, n)), over the rows the
 // next layer holds (as launch_i8_params); launch_i8_params_fold then forms
@@ -580,8 +597,23 @@ struct I8NextMinMax {
   const uint32_t *row_edge;
   int in_left, in_right;
 };
+// Static int8, fused requantize: instead of fp32 outputs the epilogue writes
+// the next Linear's quantized input -- the shifted bytes of its outputs under
+// that layer's frozen parameters `qp`, m x n (n % 128 == 0) into `xq` -- and
+// adds each row's byte sum into rowsum[row] (integer atomics: exact in any
+// order; the words must be zero when the launch starts).  `zero`: m words the
+// launch clears for the GEMM after it, a buffer no launch in flight reads.
+struct I8NextBytes {
+  int8_t *xq;
+  int32_t *rowsum;
+  int32_t *zero;
+  const void *qp;
+};
+// true when launch_i8_gemm can run layer L with an I8NextBytes epilogue
+bool i8_gemm_can_requantize(const I8Layer &L, int lda);
 int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
-                   const void *pa, float *y, int ldy, const I8NextMinMax *mm = nullptr, int *nparts = nullptr);
+                   const void *pa, float *y, int ldy, const I8NextMinMax *mm = nullptr, int *nparts = nullptr,
+                   const I8NextBytes *nb = nullptr);
 int launch_i8_params_fold(hipStream_t s, const void *part, int nparts, void *params);
 size_t i8_gemm_parts(int m, int n);
 int i8_k_align();

@@ -31,6 +31,13 @@
 // Quantising the block entering the Splice is the same as quantising the
 // spliced block: the tensor parameters depend only on min / max, and Splice +
 // Narrow read every held row of the block.
+//
+// Static int8 (ce_gpu_model_quantize_static): step 1 never runs -- every
+// layer's parameters are the model's frozen ones -- and where a GEMM's output
+// is the next layer's plain operand, step 2 moves into that GEMM's epilogue
+// (i8_epilogue_q: the next layer's bytes and row sums instead of fp32
+// outputs).  ce_gpu_model_calibrate uses step 1's two kernels on the fp32
+// programs' activations to measure the ranges (launch_i8_range).
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -113,9 +120,12 @@ __device__ __forceinline__ QP qparams(float mn, float mx) {
 }
 
 // Folds the block partials and applies ComputeQuantizationParams
-// (matrix.cc:348-362, double arithmetic) -- one block.
+// (matrix.cc:348-362, double arithmetic) -- one block.  Calibration
+// (ce_gpu_model_calibrate) passes `range` instead of `out`: the fold then
+// takes in the (min, max) already there and leaves the result in its place,
+// so one Linear's range accumulates over chunks and calls.
 __global__ __launch_bounds__(256) void params_kernel(const float2 *__restrict__ part, int nparts,
-                                                     QP *__restrict__ out) {
+                                                     QP *__restrict__ out, float2 *__restrict__ range) {
   float mn = FLT_MAX, mx = FLT_MIN;
   for (int i = threadIdx.x; i < nparts; i += 256) {
     mn = part[i].x < mn ? part[i].x : mn;
@@ -135,7 +145,12 @@ __global__ __launch_bounds__(256) void params_kernel(const float2 *__restrict__ 
       mn = wv[w].x < mn ? wv[w].x : mn;
       mx = wv[w].y > mx ? wv[w].y : mx;
     }
-    *out = qparams(mn, mx);
+    if (range) {
+      mn = range->x < mn ? range->x : mn;
+      mx = range->y > mx ? range->y : mx;
+      *range = make_float2(mn, mx);
+    }
+    if (out) *out = qparams(mn, mx);
   }
 }
 
@@ -331,20 +346,24 @@ __device__ __forceinline__ void quantize_rows_fast(const float *__restrict__ x, 
 template <int RPW>
 __global__ __launch_bounds__(256) void quantize_fast_kernel(const float *__restrict__ x, int ldx, int rows, int width,
                                                             const QP *__restrict__ params, int8_t *__restrict__ q,
-                                                            int ldq, int32_t *__restrict__ rowsum) {
+                                                            int ldq, int32_t *__restrict__ rowsum,
+                                                            int32_t *__restrict__ zero) {
   const QP p = *params;
   const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW, lane = threadIdx.x & 63;
   if (r0 >= rows) return;
+  if (zero && lane < RPW && r0 + lane < rows) zero[r0 + lane] = 0;
   quantize_rows_fast<RPW>(x, ldx, rows, width, p.scale, (float)p.zp, q, ldq, rowsum, r0, lane);
 }
 
 __global__ __launch_bounds__(256) void quantize_kernel(const float *__restrict__ x, int ldx, int rows, int width,
                                                        const int *__restrict__ row_map, int nseg,
                                                        SpliceOffsets so, const QP *__restrict__ params,
-                                                       int8_t *__restrict__ q, int ldq, int32_t *__restrict__ rowsum) {
+                                                       int8_t *__restrict__ q, int ldq, int32_t *__restrict__ rowsum,
+                                                       int32_t *__restrict__ zero) {
   const QP p = *params;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (r >= rows) return;
+  if (zero && lane == 0) zero[r] = 0;
   quantize_row(x, ldx, rows, width, row_map, nseg, so, p.scale, (float)p.zp, q, ldq, rowsum, r, lane);
 }
 
@@ -376,6 +395,12 @@ struct I8Args {
   float2 *mm_part;
   const uint32_t *row_edge;
   int mm_left, mm_right;
+  // Non-null (static int8, n % 128 == 0): no fp32 output; the epilogue writes
+  // the next layer's shifted bytes (its frozen parameters *q_qp) to qy
+  // (m x n) and adds their row sums into q_rowsum (I8NextBytes, internal.h)
+  int8_t *qy;
+  int32_t *q_rowsum, *q_zero;
+  const void *q_qp;
 };
 
 // p.off[seg] through a select chain: a runtime index into the kernel
@@ -582,6 +607,122 @@ __device__ __forceinline__ void i8_epilogue_v(const I8Args &p, const i32x16 (&ac
     return make_float2(mn, mx);
   });
   if (mm) mm_store<NT>(p.mm_part, mm2.x, mm2.y);
+}
+
+// Sum of the four signed bytes of a word.
+__device__ __forceinline__ int byte_sum(int w) {
+  const uint32_t u = (uint32_t)w;
+  return ((int)(u << 24) >> 24) + ((int)(u << 16) >> 24) + ((int)(u << 8) >> 24) + (w >> 24);
+}
+
+// Fused requantize (static int8): y exactly as i8_epilogue_v forms it, then
+// Quantize with the NEXT layer's frozen parameters (qbyte's arithmetic, the
+// function the quantize passes use: the same bytes), staged through the wave's LDS slab
+// (32 rows x TJ 32 bytes, row stride + 16 B) and stored as 16-byte row chunks
+// into that layer's operand buffer.  The chunk's lanes add their bytes and
+// one of them adds the sum to the row's word (integer atomics: a row is
+// finished by n / (TJ 32) waves of different blocks, in any order).  The
+// blocks of column tile 0 clear q_zero's rows for the launch after this one.
+// No fp32 output, no min / max partials.  LDS: NW slabs + BM words.
+template <int TI, int TJ, int BM, int NT>
+__device__ __forceinline__ void i8_epilogue_q(const I8Args &p, const i32x16 (&acc)[TI][TJ], int m0, int wrow,
+                                              int col0, int r, int h, bool first_col_tile, char *lds) {
+  constexpr int NW = NT / 64, SB = TJ * 32 + 16;  // slab row stride, bytes
+  constexpr int C16 = TJ * 2;                     // 16-byte chunks per slab row
+  static_assert(C16 == 4 && (32 * C16) % 64 == 0, "four lanes per row chunk group");
+  const QP pa = *static_cast<const QP *>(p.pa);
+  const QP pn = *static_cast<const QP *>(p.q_qp);
+  const uint32_t ca = (uint32_t)(128 - pa.zp), cb = (uint32_t)(128 - p.w_zp);
+  const uint32_t kterm = (uint32_t)p.k * ca * cb;
+  const float cscale = pa.scale * p.w_scale;  // matrix.cc:404-405
+  const float nzp = (float)pn.zp;
+  float nrs = CATEARS_I8_QDIV ? 1.0f / pn.scale : 0.0f;  // as quantize_row
+  if (__builtin_isinf(nrs) || __builtin_isnan(nrs)) nrs = 0.0f;
+  uint32_t *srs = reinterpret_cast<uint32_t *>(lds + NW * 32 * SB);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int8_t *slab = reinterpret_cast<int8_t *>(lds) + wave * 32 * SB;
+  __syncthreads();
+  for (int t = threadIdx.x; t < BM; t += NT) {
+    const int row = m0 + t;
+    uint32_t sum = 0;
+#pragma unroll
+    for (int sg = 0; sg < 8; ++sg) {
+      if (sg < p.nseg) {
+        int src = row + p.off[sg];
+        src = src < 0 ? 0 : (src > p.m - 1 ? p.m - 1 : src);
+        sum += (uint32_t)p.rowsum[src];
+      }
+    }
+    srs[t] = cb * sum;
+    if (first_col_tile && p.q_zero && row < p.m) p.q_zero[row] = 0;
+  }
+  __syncthreads();
+  uint32_t cterm[TJ];
+  float bias[TJ], sc[TJ], of[TJ];
+#pragma unroll
+  for (int j = 0; j < TJ; ++j) {
+    const int col = col0 + j * 32 + r;  // n % 128 == 0: every column exists
+    cterm[j] = ca * (uint32_t)p.colsum[col] + kterm;
+    bias[j] = p.bias ? p.bias[col] : 0.0f;
+    sc[j] = p.bn_scale ? p.bn_scale[col] : 1.0f;
+    of[j] = p.bn_offset ? p.bn_offset[col] : 0.0f;
+  }
+  with_post_mode(p.post_mode, [&](auto M) {
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        // qbyte over the lane's 16 outputs of column j with its fallback
+        // test once per wave (as quantize_rows_fast): the corrected
+        // quotients first, the division only where one is not finite
+        float yv[16], qv[16];
+        bool bad = nrs == 0.0f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int rr = (e & 3) + 8 * (e >> 2) + 4 * h;  // row within the slab
+          const uint32_t v = (uint32_t)acc[i][j][e] + srs[wrow + i * 32 + rr] + cterm[j];
+          float y = (float)(int32_t)v * cscale;
+          y = y + bias[j];
+          y = apply_post<decltype(M)::value>(y, sc[j], of[j], p.post, p.npost);
+          const float q0 = y * nrs;
+          const float qq = __builtin_fmaf(__builtin_fmaf(-pn.scale, q0, y), nrs, q0);
+          bad |= __builtin_isinf(qq) || __builtin_isnan(qq);
+          yv[e] = y;
+          qv[e] = qq;
+        }
+        if (__builtin_amdgcn_ballot_w64(bad)) {
+          if (bad) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+              if (nrs == 0.0f || __builtin_isinf(qv[e]) || __builtin_isnan(qv[e])) qv[e] = yv[e] / pn.scale;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int rr = (e & 3) + 8 * (e >> 2) + 4 * h;
+          float w = qv[e] + nzp;
+          w = (255.0f < w) ? 255.0f : w;  // std::min(w, 255.0f)
+          w = (0.0f < w) ? w : 0.0f;      // std::max(0.0f, w)
+          slab[rr * SB + j * 32 + r] = (int8_t)((int)(uint8_t)roundf(w) - 128);
+        }
+      }
+      wave_lds_sync();
+#pragma unroll
+      for (int q = 0; q < 32 * C16 / 64; ++q) {
+        const int idx = lane + 64 * q, rr = idx / C16, c = idx % C16;
+        const int row = m0 + wrow + i * 32 + rr;
+        const i32x4 v = *reinterpret_cast<const i32x4 *>(slab + rr * SB + 16 * c);
+        int sum = byte_sum(v[0]) + byte_sum(v[1]) + byte_sum(v[2]) + byte_sum(v[3]);
+        sum += __shfl_xor(sum, 1, 64);
+        sum += __shfl_xor(sum, 2, 64);
+        if (row < p.m) {
+          *reinterpret_cast<i32x4 *>(p.qy + (int64_t)row * p.n + col0 + 16 * c) = v;
+          if (c == 0) atomicAdd(p.q_rowsum + row, sum);
+        }
+      }
+      wave_lds_sync();
+    }
+  });
 }
 
 __global__ __launch_bounds__(256, 2) void gemm_i8_nnet_kernel(I8Args p) {
@@ -971,6 +1112,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void gemm_i8_pipe_kernel(I8Args 
     __builtin_amdgcn_sched_barrier(0);
   }
 
+  if constexpr (TJ == 2) {
+    static_assert(NW * 32 * (TJ * 32 + 16) + BM * 4 <= STAGES * STAGE, "byte slabs + row sums in the stages");
+    if (p.qy) {
+      i8_epilogue_q<TI, TJ, BM, 64 * NW>(p, acc, m0, wm * TI * 32, n0 + wn * TJ * 32, r, h, tn == 0,
+                                         reinterpret_cast<char *>(smem));
+      return;
+    }
+  }
   // slabs + row sums in the stages; one 64-row held-row mask per wave
   constexpr bool kVecFits = TI == 2 && NW * 32 * (TJ * 32 + 8) * 4 + BM * 4 <= STAGES * STAGE;
   if constexpr (kVecFits) {
@@ -1210,7 +1359,20 @@ int launch_i8_params(hipStream_t s, const float *x, int ldx, int rows, int width
   hipLaunchKernelGGL(minmax_kernel, dim3(blocks), dim3(256), 0, s, x, ldx, rows, width, row_map, row_edge, in_left,
                      in_right, static_cast<float2 *>(part));
   hipLaunchKernelGGL(params_kernel, dim3(1), dim3(256), 0, s, static_cast<const float2 *>(part), blocks,
-                     static_cast<QP *>(params));
+                     static_cast<QP *>(params), static_cast<float2 *>(nullptr));
+  CE_HIP(hipGetLastError());
+  return CE_GPU_OK;
+}
+
+// Calibration: folds the (min, max) of the held rows of a layer input into
+// range[0..1] (device; the same two kernels as launch_i8_params).
+int launch_i8_range(hipStream_t s, const float *x, int ldx, int rows, int width, const int *row_map,
+                    const uint32_t *row_edge, int in_left, int in_right, void *part, float *range) {
+  const int blocks = std::max(1, std::min(kMinmaxBlocks, (rows + 3) / 4));
+  hipLaunchKernelGGL(minmax_kernel, dim3(blocks), dim3(256), 0, s, x, ldx, rows, width, row_map, row_edge, in_left,
+                     in_right, static_cast<float2 *>(part));
+  hipLaunchKernelGGL(params_kernel, dim3(1), dim3(256), 0, s, static_cast<const float2 *>(part), blocks,
+                     static_cast<QP *>(nullptr), reinterpret_cast<float2 *>(range));
   CE_HIP(hipGetLastError());
   return CE_GPU_OK;
 }
@@ -1218,7 +1380,7 @@ int launch_i8_params(hipStream_t s, const float *x, int ldx, int rows, int width
 size_t i8_params_scratch_bytes() { return sizeof(float2) * kMinmaxBlocks + 256; }
 
 int launch_i8_quantize(hipStream_t s, const float *x, int ldx, int rows, int width, const int *row_map, int nseg,
-                       const int *offs, const void *params, int8_t *q, int ldq, int32_t *rowsum) {
+                       const int *offs, const void *params, int8_t *q, int ldq, int32_t *rowsum, int32_t *zero) {
   SpliceOffsets so = {};
   for (int i = 0; i < nseg; ++i) so.off[i] = offs[i];
   // Plain-mode layers (every layer after the first) go through
@@ -1232,27 +1394,46 @@ int launch_i8_quantize(hipStream_t s, const float *x, int ldx, int rows, int wid
                      (reinterpret_cast<uintptr_t>(q) & 3) == 0;
   if (rows > 0 && plain && qfast == 1) {
     hipLaunchKernelGGL(quantize_fast_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, s, x, ldx, rows, width,
-                       static_cast<const QP *>(params), q, ldq, rowsum);
+                       static_cast<const QP *>(params), q, ldq, rowsum, zero);
   } else if (rows > 0 && plain && qfast == 2) {
     hipLaunchKernelGGL(quantize_fast_kernel<2>, dim3((rows + 7) / 8), dim3(256), 0, s, x, ldx, rows, width,
-                       static_cast<const QP *>(params), q, ldq, rowsum);
+                       static_cast<const QP *>(params), q, ldq, rowsum, zero);
   } else if (rows > 0)
     hipLaunchKernelGGL(quantize_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, ldx, rows, width, row_map, nseg,
-                       so, static_cast<const QP *>(params), q, ldq, rowsum);
+                       so, static_cast<const QP *>(params), q, ldq, rowsum, zero);
   CE_HIP(hipGetLastError());
   return CE_GPU_OK;
 }
 
 int launch_i8_params_fold(hipStream_t s, const void *part, int nparts, void *params) {
   hipLaunchKernelGGL(params_kernel, dim3(1), dim3(256), 0, s, static_cast<const float2 *>(part), nparts,
-                     static_cast<QP *>(params));
+                     static_cast<QP *>(params), static_cast<float2 *>(nullptr));
   CE_HIP(hipGetLastError());
   return CE_GPU_OK;
 }
 
+// 16: measured best on TDNN-S, frame batch 8192 (tools/i8_sweep.sh)
+static int i8_gemm_variant() {
+  static const int v = CE_KNOB("CATEARS_I8_GEMM", 16);
+  return v;
+}
+
+// the requantize epilogue is gemm_i8_pipe_kernel's (variants 16 and 17)
+bool i8_gemm_can_requantize(const I8Layer &L, int lda) {
+  const int v = i8_gemm_variant();
+  return (v == 16 || v == 17) && L.n % 128 == 0 && L.kpad % 128 == 0 && L.a_din % 128 == 0 && lda % 16 == 0;
+}
+
 int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
-                   const void *pa, float *y, int ldy, const I8NextMinMax *mm, int *nparts) {
+                   const void *pa, float *y, int ldy, const I8NextMinMax *mm, int *nparts, const I8NextBytes *nb) {
   I8Args p = {};
+  if (nb) {
+    if (!i8_gemm_can_requantize(L, lda)) return fail(CE_GPU_EINVAL, "int8 GEMM: no requantize epilogue for this layer");
+    p.qy = nb->xq;
+    p.q_rowsum = nb->rowsum;
+    p.q_zero = nb->zero;
+    p.q_qp = nb->qp;
+  }
   if (mm) {
     p.mm_part = static_cast<float2 *>(mm->part);
     p.row_edge = mm->row_edge;
@@ -1285,8 +1466,7 @@ int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, in
   static const int vec_epi = CE_KNOB("CATEARS_I8_EPI", 1);
   p.vec_epi = vec_epi && L.n % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
 
-  // 16: measured best on TDNN-S, frame batch 8192 (tools/i8_sweep.sh)
-  static const int use_glds = CE_KNOB("CATEARS_I8_GEMM", 16);
+  const int use_glds = i8_gemm_variant();
   if (use_glds && p.kpad % 128 == 0 && p.din % 128 == 0 && lda % 16 == 0) {
     auto go = [&](auto kern, int bm, int bn, int threads = 256) {
       p.tiles_n = (L.n + bn - 1) / bn;

@@ -58,6 +58,7 @@ struct ce_gpu_sessions {
   ce_gpu_ctx *ctx = nullptr;
   const ce_gpu_model *m = nullptr;
   const float *gstats = nullptr;
+  bool static_int8 = false;    // the model's form at create
   int n_slots = 0, max_chunk = 0, L = 0, R = 0;
   int max_frames = 0;          // most frames one push of one slot can complete
   int raw_cap = 0, norm_cap = 0;
@@ -84,7 +85,11 @@ int push_t(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_nu
   if (n == 0) return CE_GPU_OK;
   if (n > s->n_slots) return fail(CE_GPU_EINVAL, "sessions_push: more pushes than slots");
   const ce_gpu_model *m = s->m;
-  if (m->int8) return fail(CE_GPU_ENOTSUP, "sessions_push: the model was quantized (int8 rows depend on the batch)");
+  if (m->int8 && !m->int8_static)
+    return fail(CE_GPU_ENOTSUP, "sessions_push: the model was quantized (int8 rows depend on the batch)");
+  // the workspaces were sized for the form the model had at sessions_create
+  if (m->int8_static != s->static_int8)
+    return fail(CE_GPU_EINVAL, "sessions_push: the model was quantized after sessions_create");
   const int L = s->L, R = s->R;
 
   // 1. every count of the push, by arithmetic alone
@@ -277,7 +282,9 @@ int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *
   *out = nullptr;
   if (!ctx || !m || n_slots < 1 || n_slots > 65535 || max_chunk_samples < 1)
     return fail(CE_GPU_EINVAL, "sessions_create: bad argument");
-  if (m->int8)
+  // a static int8 model (frozen activation parameters) scores a row from its
+  // own input rows alone, like the fp32 forms
+  if (m->int8 && !m->int8_static)
     return fail(CE_GPU_ENOTSUP, "sessions_create: an int8 model's rows depend on the batch they are scored in");
   if (m->input_dim != kMel) return fail(CE_GPU_EINVAL, "sessions_create: nnet input is not 40-dim fbank");
   if (!m->log_prior.ptr) return fail(CE_GPU_EINVAL, "sessions_create: needs a model loaded with a prior");
@@ -290,6 +297,7 @@ int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *
   if (!s) return fail(CE_GPU_ENOMEM, "out of host memory");
   s->ctx = ctx;
   s->m = m;
+  s->static_int8 = m->int8_static;
   s->gstats = d_global_stats;
   s->n_slots = n_slots;
   s->max_chunk = max_chunk_samples;

@@ -35,6 +35,8 @@ ABI = [
     "ce_gpu_sum_f64_many", "ce_gpu_trace_mark", "ce_gpu_nnet_check_mem",
     "ce_gpu_sessions_create", "ce_gpu_sessions_destroy", "ce_gpu_sessions_reset", "ce_gpu_sessions_push",
     "ce_gpu_sessions_push_s16", "ce_gpu_debug_counters",
+    "ce_gpu_quant_params_from_range", "ce_gpu_model_calibrate", "ce_gpu_model_quantize_static",
+    "ce_gpu_model_quant_params",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -118,6 +120,10 @@ def lib():
         "ce_gpu_sessions_reset": (ci, [vp, ci]),
         "ce_gpu_sessions_push": (ci, [vp, ci, pi32, pi32, pi32, vp, vp, i64, pi32]),
         "ce_gpu_sessions_push_s16": (ci, [vp, ci, pi32, pi32, pi32, vp, vp, i64, pi32]),
+        "ce_gpu_quant_params_from_range": (ci, [ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float), pi32]),
+        "ce_gpu_model_calibrate": (ci, [vp, vp, vp, vp, ci, vp]),
+        "ce_gpu_model_quantize_static": (ci, [vp, vp, vp, ci]),
+        "ce_gpu_model_quant_params": (ci, [vp, vp, vp, ci, pi]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -258,6 +264,35 @@ class Model:
         check(lib().ce_gpu_model_quantize(ctx.h, self.h))
         return self
 
+    def calibrate(self, ctx, plan, feats, ranges=None):
+        """Per-Linear input (min, max) over the plan's utterances
+        (ce_gpu_model_calibrate) -> (num_linear, 2) float32.  `ranges`: an
+        earlier result to fold into (a corpus fed batch by batch)."""
+        r = np.zeros((self.num_linear, 2), np.float32) if ranges is None else \
+            np.array(ranges, np.float32).reshape(self.num_linear, 2)
+        check(lib().ce_gpu_model_calibrate(ctx.h, self.h, plan.h, _ptr(feats), int(ranges is not None),
+                                           r.ctypes.data_as(ctypes.c_void_p)))
+        return r
+
+    def quantize_static(self, ctx, ranges):
+        """Switch to static int8: frozen activation parameters from the
+        calibrated ranges (ce_gpu_model_quantize_static)."""
+        r = np.ascontiguousarray(ranges, np.float32)
+        if r.ndim != 2 or r.shape[1] != 2:
+            raise ValueError("ranges must be (num_linear, 2)")
+        check(lib().ce_gpu_model_quantize_static(ctx.h, self.h, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]))
+        return self
+
+    def quant_params(self):
+        """(scale float32[n], zero_point int32[n]) of a static int8 model
+        (n = 0 otherwise; ce_gpu_model_quant_params)."""
+        n = ctypes.c_int()
+        check(lib().ce_gpu_model_quant_params(self.h, None, None, 0, ctypes.byref(n)))
+        s, z = np.zeros(n.value, np.float32), np.zeros(n.value, np.int32)
+        check(lib().ce_gpu_model_quant_params(self.h, s.ctypes.data_as(ctypes.c_void_p),
+                                              z.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return s, z
+
     def set_gemm(self, mode):
         """Matrix-core form of the fp32 Linear layers: "fp32" (fp32 MFMA),
         "bf16x6" (three-plane bf16 split on the way into LDS, six products),
@@ -291,6 +326,14 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+def quant_params_from_range(mn, mx):
+    """(scale, zero_point) of the reference's Quantize for a tensor with these
+    extremes (ce_gpu_quant_params_from_range; needs no device)."""
+    s, z = ctypes.c_float(), ctypes.c_int32()
+    check(lib().ce_gpu_quant_params_from_range(float(mn), float(mx), ctypes.byref(s), ctypes.byref(z)))
+    return np.float32(s.value), int(z.value)
 
 
 def profile_anchor(device, stream):

@@ -64,7 +64,9 @@ const char *ce_gpu_last_error(void);
  * fbank mode (ce_gpu_ctx_set_fbank); 0.4 ce_gpu_sum_f64(_many) and
  * ce_gpu_ctx_set_wide_tiles; 0.5 no environment switch in the product
  * library; 0.6 adds the device-resident sessions (ce_gpu_sessions_*) and
- * ce_gpu_debug_counters. */
+ * ce_gpu_debug_counters; 0.7 adds calibrated static int8
+ * (ce_gpu_quant_params_from_range, ce_gpu_model_calibrate,
+ * ce_gpu_model_quantize_static, ce_gpu_model_quant_params). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -218,8 +220,63 @@ int ce_gpu_model_info(const ce_gpu_model *m, int *left_context, int *right_conte
  * ce_gpu_am_forward / ce_gpu_score an utterance's int8 log-likelihoods depend
  * on which utterances share its packed chunk.  ce_gpu_nnet_propagate_blocks
  * quantizes every block on its own instead, so there each block gets exactly
- * the rows it gets alone (the AcousticModel batcher's contract). */
+ * the rows it gets alone (the AcousticModel batcher's contract).
+ * A model in the static int8 form (below) is refused with CE_GPU_EINVAL. */
 int ce_gpu_model_quantize(ce_gpu_ctx *ctx, ce_gpu_model *m);
+
+/* ---- calibrated static int8: one frozen (scale, zero point) per Linear ---
+ *
+ * The dynamic int8 form above takes every activation tensor's parameters
+ * from the block being scored.  The static form measures each Linear's input
+ * range once on representative audio (ce_gpu_model_calibrate), freezes the
+ * parameters of that range in the model (ce_gpu_model_quantize_static) and
+ * quantizes every activation with them.
+ *
+ * Contract: for a static int8 model, every row that ce_gpu_am_forward,
+ * ce_gpu_score(_s16), ce_gpu_nnet_propagate, ce_gpu_nnet_propagate_blocks and
+ * ce_gpu_sessions_push produce depends only on the input rows it covers.
+ * Its bits are the same whatever shares its chunk, whatever the plan's
+ * max_rows, and however the audio is pushed; ce_gpu_nnet_propagate windows
+ * long blocks and ce_gpu_nnet_propagate_blocks scores all blocks in one
+ * launch sequence, as for fp32.  Values outside the calibrated range clamp
+ * to byte 0 or 255 (Quantize's clamp, src/matrix.cc:378-386).  The dynamic
+ * int8 form keeps its definition, its bits and its CE_GPU_ENOTSUP in
+ * sessions. */
+
+/* The (scale, zero point) the reference's Quantize picks for a tensor whose
+ * extremes are min and max: FindMinMax's seeding (a max below FLT_MIN becomes
+ * FLT_MIN, src/matrix.cc:331-345) followed by ComputeQuantizationParams
+ * (src/matrix.cc:348-362): scale = (max - min) / 255 in double, stored as
+ * float; zero_point = round(-min / scale), unclamped.  Needs no device.
+ * Non-finite input, min > max, or a scale that is not finite and positive:
+ * CE_GPU_EINVAL. */
+int ce_gpu_quant_params_from_range(float min, float max, float *scale, int32_t *zero_point);
+
+/* Runs the plan's utterances (d_feats: the plan's feature rows, as for
+ * ce_gpu_am_forward) through the model in its current GEMM mode
+ * (CE_GPU_GEMM_FP32 or CE_GPU_GEMM_BF16X6; the plane modes keep no fp32
+ * activations: CE_GPU_ENOTSUP) and folds, per Linear i, the min / max of that
+ * Linear's input -- the block entering its Splice, over the rows the
+ * reference chain holds there, with FindMinMax's comparisons -- into
+ * h_ranges[2 i] and h_ranges[2 i + 1] (num_linear of ce_gpu_model_info
+ * pairs).  accumulate = 0 starts from FindMinMax's seeds (FLT_MAX, FLT_MIN);
+ * accumulate = 1 folds into the caller's values, so a corpus can be fed batch
+ * by batch.  m must not be quantized.  Host-synchronous; allocates. */
+int ce_gpu_model_calibrate(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan *p, const float *d_feats,
+                           int accumulate, float *h_ranges);
+
+/* Switch a loaded model to the static int8 form: weights quantized exactly
+ * as ce_gpu_model_quantize does, activations of Linear i with
+ * ce_gpu_quant_params_from_range(h_ranges[2 i], h_ranges[2 i + 1]).
+ * n_ranges != num_linear or a bad range: CE_GPU_EINVAL, model unchanged.  A
+ * model already quantized (either form): CE_GPU_EINVAL.  Irreversible. */
+int ce_gpu_model_quantize_static(ce_gpu_ctx *ctx, ce_gpu_model *m, const float *h_ranges, int n_ranges);
+
+/* The frozen activation parameters of a static int8 model, one per Linear
+ * (for logging and tests): copies min(capacity, *count) of each; *count = 0
+ * for a model that is not static int8.  Either array may be NULL. */
+int ce_gpu_model_quant_params(const ce_gpu_model *m, float *h_scale, int32_t *h_zero_point, int capacity,
+                              int *count);
 
 /* Matrix-core form of the fp32 Linear layers (LinearLayer::Propagate ->
  * MatMat -> cblas_sgemm, src/nnet.cc:22-36, src/matrix.cc:300-323):
@@ -243,8 +300,10 @@ int ce_gpu_model_quantize(ce_gpu_ctx *ctx, ce_gpu_model *m);
  * Linear's input width after the first a multiple of 32, output widths
  * multiples of 4, every ReLU/BatchNorm fused into a Linear), else FP32.
  * F16X3 (22-23 significant bits per operand, not a full fp32 significand)
- * is opt-in.  Environment CATEARS_NNET_GEMM=fp32|bf16x6|bf16x6p|f16x3 overrides the
- * default.  Setting a mode the model does not allow returns CE_GPU_ENOTSUP. */
+ * is opt-in.  Only the experiments library (make EXPERIMENTS=1) reads the
+ * environment's CATEARS_NNET_GEMM (0-3, the numbers below) as the default;
+ * the product library reads no environment.  Setting a mode the model does
+ * not allow returns CE_GPU_ENOTSUP. */
 #define CE_GPU_GEMM_FP32 0
 #define CE_GPU_GEMM_BF16X6 1
 #define CE_GPU_GEMM_F16X3 2

@@ -14,7 +14,10 @@ in blocks of `ticks` ticks, `rounds` times, after a warm-up block of each;
 reported are the median and the 10th / 90th percentile over all timed ticks.
 Both legs compute the same rows (checked once per N, bit for bit).
 
-  python tools/session_latency.py [ticks] [rounds]      -> JSON lines"""
+  python tools/session_latency.py [ticks] [rounds]      -> JSON lines
+  python tools/session_latency.py --static-int8 [ticks] [rounds]
+      the 64-stream push only: the bf16x6 latency-mode model beside a static
+      int8 model (ce_gpu_model_quantize_static), see static_int8()"""
 import json
 import os
 import sys
@@ -131,5 +134,53 @@ def main(ticks=100, rounds=3):
         print(json.dumps(rec), flush=True)
 
 
+def static_int8(ticks=100, rounds=3, n=64):
+    """The n-stream push with a static int8 model (calibrated on 12 s of the
+    synthetic audio, no CMVN) beside the bf16x6 latency-mode push of main():
+    two contexts, one session set each, alternating blocks of `ticks` ticks."""
+    mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
+    conf = synth.write_model(mdir, "tdnn-s")
+    ctx_x6 = gpu.Context(0)
+    ctx_x6.set_latency(True)
+    ctx_i8 = gpu.Context(0)
+    m_x6, m_i8 = gpu.Model(ctx_x6, conf), gpu.Model(ctx_i8, conf)
+    cal = [synth.pcm(2900 + i, 48000) for i in range(4)]
+    plan = gpu.Plan(ctx_i8, [len(w) for w in cal], m_i8)
+    ranges = m_i8.calibrate(ctx_i8, plan, gpu.fbank(ctx_i8, plan, torch.from_numpy(np.concatenate(cal)).cuda()))
+    m_i8.quantize_static(ctx_i8, ranges)
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "model": "tdnn-s", "chunk_samples": CHUNK,
+                      "slots": n, "ticks": ticks, "rounds": rounds, "legs": ["bf16x6 latency", "static int8"],
+                      "version": gpu.lib().ce_gpu_version().decode()}), flush=True)
+    total = CHUNK * ticks * (rounds + 1)
+    waves = [synth.pcm(3000 + s, total) for s in range(n)]
+    legs = [(ctx_x6, gpu.Sessions(ctx_x6, m_x6, n, CHUNK)), (ctx_i8, gpu.Sessions(ctx_i8, m_i8, n, CHUNK))]
+    out = torch.empty((n * 16, m_x6.num_pdfs), dtype=torch.float32, device="cuda")
+    slots, times = list(range(n)), ([], [])
+    counters = None
+    for r in range(rounds + 1):
+        for k, (ctx, sess) in enumerate(legs):
+            for t in range(r * ticks, (r + 1) * ticks):
+                pcm = np.concatenate([w[t * CHUNK:(t + 1) * CHUNK] for w in waves])
+                t0 = time.perf_counter()
+                sess.push(slots, torch.from_numpy(pcm).cuda(), [CHUNK] * n, out=out)
+                ctx.synchronize()
+                if r:  # block 0 is the warm-up
+                    times[k].append(time.perf_counter() - t0)
+        if r == 0:
+            counters = gpu.debug_counters()
+    rec = {"slots": n, "timed_ticks": len(times[0]), "pushes_allocated_nothing": gpu.debug_counters() == counters}
+    for name, v in (("bf16x6_latency", times[0]), ("static_int8", times[1])):
+        rec[name] = {"median_us": round(pct(v, 50) * 1e6, 1), "p10_us": round(pct(v, 10) * 1e6, 1),
+                     "p90_us": round(pct(v, 90) * 1e6, 1)}
+    rec["static_int8_over_bf16x6"] = round(pct(times[1], 50) / pct(times[0], 50), 2)
+    print(json.dumps(rec), flush=True)
+    for _, sess in legs:
+        sess.close()
+
+
 if __name__ == "__main__":
-    main(*[int(v) for v in sys.argv[1:3]])
+    nums = [int(v) for v in sys.argv[1:] if not v.startswith("--")][:2]
+    if "--static-int8" in sys.argv[1:]:
+        static_int8(*nums)
+    else:
+        main(*nums)
