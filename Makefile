@@ -39,7 +39,7 @@ KERNELS := $(wildcard $(SRC)/kernels/*.hip)
 HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
         $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
-HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/cmvn_ops.h
+HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h
 
 all: $(LIB) oracle
 
@@ -140,7 +140,13 @@ $(FUZZASAN): tests/native/parse_fuzz.cc $(SRC)/model_io.cc $(SRC)/model_io.h $(H
 	    $(HOST)/src/linalg.cc $(wildcard $(HOST)/compat_src/*.cc) \
 	    -Lcatears_amd/lib -lcatears_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(CURDIR)/catears_amd/lib \
 	    -Wl,-rpath,/opt/rocm/lib
-sanitize: $(COMPATASAN) $(FUZZASAN)
+# the gpu_int8_ranges key (model_io.cc's read_int8_ranges: configuration +
+# VEC0) over truncated and corrupted ranges files; model_io.cc alone, no HIP
+RANGESASAN := build/bin/ranges_fuzz_asan
+$(RANGESASAN): tests/native/ranges_fuzz.cc $(SRC)/model_io.cc $(SRC)/model_io.h include/catears_gpu.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANFLAGS) -std=c++17 -Wall -Iinclude -I$(SRC) -o $@ tests/native/ranges_fuzz.cc $(SRC)/model_io.cc
+sanitize: $(COMPATASAN) $(FUZZASAN) $(RANGESASAN)
 .PHONY: sanitize
 
 host: $(PKLIB) $(PKTEST) $(COMPATTEST)

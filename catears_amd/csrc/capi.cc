@@ -621,6 +621,18 @@ int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees) {
   return CE_GPU_OK;
 }
 
+int ce_gpu_debug_i8_latency_launches(int64_t *gemms) {
+  if (gemms) *gemms = i8_lat_launch_count();
+  return CE_GPU_OK;
+}
+
+int ce_gpu_i8_latency_plan(int kpad, int n, int rows, int *slices, int *k_steps_per_slice) {
+  if (!slices || !k_steps_per_slice) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (kpad <= 0 || n <= 0 || rows <= 0) return fail(CE_GPU_EINVAL, "i8_latency_plan: kpad, n and rows must be positive");
+  i8_lat_plan(kpad, n, rows, slices, k_steps_per_slice);
+  return CE_GPU_OK;
+}
+
 int ce_gpu_trace_mark(int device, void *stream, int tag) {
   if (device < 0 || device >= 64 || tag < 1 || tag > 64) return fail(CE_GPU_EINVAL, "bad device or tag");
   CE_HIP(hipSetDevice(device));
@@ -684,6 +696,16 @@ int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_mo
   ce_gpu_model *m = nullptr;
   CE_TRY(load_model(ctx, nnet, prior, left, right, tid2pdf, &m));
   m->chunk = chunk;
+  // gpu_int8_ranges: static int8 from the config (model_io.cc)
+  std::unique_ptr<ce_gpu_model> own(m);
+  std::string ranges_path;
+  std::vector<float> ranges;
+  CE_TRY(read_int8_ranges(cf, &ranges, &ranges_path));
+  if (!ranges.empty()) {
+    const int rc = ce_gpu_model_quantize_static(ctx, m, ranges.data(), (int)(ranges.size() / 2));
+    if (rc != CE_GPU_OK) return fail(rc, ranges_path + ": " + last_error());
+  }
+  own.release();
   *out = m;
   return CE_GPU_OK;
 }
@@ -1412,15 +1434,33 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
     }
     const I8Layer *N = si + 1 < m->steps.size() && m->steps[si + 1].is_gemm ? &m->steps[si + 1].i8 : nullptr;
     const bool fuse = fused_ok && N && N->in_width == L.n && !N->spliced && i8_gemm_can_requantize(L, ldq);
+    // latency mode: the split-K pair where the slice rule gives it this layer
+    // at this row count (the same bits, and the same row-sum rotation: either
+    // producer reads rs[rc], adds into the cleared rs[rc + 1], clears rs[rc + 2])
+    int lat_slices = 0, lat_per = 0;
+    if (ctx->latency && i8_lat_eligible(L, ldq)) i8_lat_plan(L.kpad, L.n, rows, &lat_slices, &lat_per);
+    size_t lat_words = 0;
+    if (lat_slices > 0) {
+      lat_words = i8_lat_part_words(rows, L.n, lat_slices);
+      CE_TRY(ensure_lat_part(ctx, lat_words));
+    }
     ProfScope prof(ctx, CE_GPU_PROF_GEMM);
     if (fuse) {
       const I8NextBytes nb = {xq[qc ^ 1], rs[(rc + 1) % 3], rs[(rc + 2) % 3], N->qp};
-      CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, nullptr, nullptr, &nb));
+      if (lat_slices > 0)
+        CE_TRY(launch_i8_lat(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, &nb,
+                             ctx->lat_part.as<int32_t>(), lat_words));
+      else
+        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, nullptr, nullptr, &nb));
       qc ^= 1;
       rc = (rc + 1) % 3;
       x = nullptr;
     } else {
-      CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n));
+      if (lat_slices > 0)
+        CE_TRY(launch_i8_lat(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n, nullptr,
+                             ctx->lat_part.as<int32_t>(), lat_words));
+      else
+        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n));
       x = buf[cur];
       cur ^= 1;
     }
@@ -1556,7 +1596,19 @@ int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows) {
     size_t q_bytes = 0, rs_bytes = 0;
     i8_static_scratch(m, rows, &q_bytes, &rs_bytes);
     CE_TRY(ensure_workspace(ctx, 2 * (size_t)rows * m->max_width));
-    return ensure_scratch(ctx, 2 * q_bytes + 3 * rs_bytes);
+    CE_TRY(ensure_scratch(ctx, 2 * q_bytes + 3 * rs_bytes));
+    // the latency pair's partials: the slice rule depends on the row count,
+    // so the largest over every count a later call may bring
+    size_t lat = 0;
+    for (const Step &st : m->steps) {
+      if (!st.is_gemm || !i8_lat_eligible(st.i8, st.i8.spliced ? st.i8.kpad : st.i8.in_width)) continue;
+      for (int r = 1; r <= std::min(rows, kI8LatMaxRows); ++r) {
+        int slices = 0, per = 0;
+        i8_lat_plan(st.i8.kpad, st.i8.n, r, &slices, &per);
+        lat = std::max(lat, i8_lat_part_words(r, st.i8.n, slices));
+      }
+    }
+    return lat ? ensure_lat_part(ctx, lat) : CE_GPU_OK;
   }
   const size_t r = (size_t)rows;
   size_t ws = 2 * r * m->max_width, scratch = 0, lat = 0;

@@ -614,6 +614,27 @@ bool i8_gemm_can_requantize(const I8Layer &L, int lda);
 int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
                    const void *pa, float *y, int ldy, const I8NextMinMax *mm = nullptr, int *nparts = nullptr,
                    const I8NextBytes *nb = nullptr);
+// Latency mode of the static int8 GEMMs (kernels/nnet_i8_lat.hip): K split
+// into slices, every slice's int32 partial tile stored, then summed by a
+// reduce kernel that forms the outputs (fp32, or the next layer's bytes and
+// row sums with `nb`) with the throughput epilogues' arithmetic (i8_ops.h).
+// Integer sums modulo 2^32: the same bits as launch_i8_gemm for any split.
+// i8_lat_plan is the slice rule -- the dispatcher's, the workspace sizing's
+// and ce_gpu_i8_latency_plan's: slices = 0 means the throughput kernel
+// (kpad not a multiple of 128, or rows above the crossover); otherwise every
+// slice holds `per` 64-byte k-steps but the last, which holds at least one.
+// kI8LatMaxRows: the largest row count of the sweep 70 / 140 / 280 / 640 /
+// 1024 / 2048 at which the pair was measured faster than the throughput
+// kernel (TDNN-S per call: 176.1 against 177.6 us at 280 rows, 261.9 against
+// 180.0 us at 640; DESIGN.md §8, profiles/r08_i8_latency_sweep.txt).
+constexpr int kI8LatMaxRows = 280;
+void i8_lat_plan(int kpad, int n, int rows, int *slices, int *per);
+size_t i8_lat_part_words(int rows, int n, int slices);
+bool i8_lat_eligible(const I8Layer &L, int lda);
+int64_t i8_lat_launch_count();  // i8_lat_gemm_kernel launches of this process
+// part: i8_lat_part_words(m, L.n, slices) int32 words, 16-byte aligned
+int launch_i8_lat(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
+                  const void *pa, float *y, int ldy, const I8NextBytes *nb, int32_t *part, size_t part_words);
 int launch_i8_params_fold(hipStream_t s, const void *part, int nparts, void *params);
 size_t i8_gemm_parts(int m, int n);
 int i8_k_align();

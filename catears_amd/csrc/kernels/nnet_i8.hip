@@ -43,6 +43,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "../i8_ops.h"
 #include "../internal.h"
 #include "../tile_order.h"
 
@@ -105,11 +106,6 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float *__restrict__ x
   }
 }
 
-struct QP {
-  float scale;
-  int32_t zp;
-};
-
 // ComputeQuantizationParams (matrix.cc:348-362) of a folded (min, max)
 __device__ __forceinline__ QP qparams(float mn, float mx) {
   const double scale = (mx - mn) / 255.0;
@@ -154,41 +150,6 @@ __global__ __launch_bounds__(256) void params_kernel(const float2 *__restrict__ 
   }
 }
 
-// The corrected reciprocal product below is the default: 0 differing
-// quotients from IEEE division over 68.7e9 random pairs on the GPU
-// (tools/probes/qdiv_probe.hip, denormal scales included), the int8 and
-// parity tests bit-exact with it, the C5 checksum unchanged, C5 +1.2 %
-// (profiles/r05z21_i8_qdiv.txt).  -DCATEARS_I8_QDIV=0 builds the division.
-#ifndef CATEARS_I8_QDIV
-#define CATEARS_I8_QDIV 1
-#endif
-
-// Quantize (matrix.cc:378-386) of one element -> shifted signed byte.
-// CATEARS_I8_QDIV=1: x / scale as q0 = x * r, r = 1 / scale (correctly
-// rounded), corrected once, q = fma(fma(-scale, q0, x), r, q0) (Markstein's
-// correction: the correctly rounded quotient when r is the correctly rounded
-// reciprocal and nothing overflows); rscale == 0 (1 / scale not finite: a
-// denormal scale) and non-finite results fall back to the division.
-__device__ __forceinline__ int qbyte(float x, float scale, float zp, float rscale = 0.0f) {
-#if CATEARS_I8_QDIV
-  float q;
-  if (rscale != 0.0f) {
-    const float q0 = x * rscale;
-    q = __builtin_fmaf(__builtin_fmaf(-scale, q0, x), rscale, q0);
-    if (__builtin_isinf(q) || __builtin_isnan(q)) q = x / scale;
-  } else {
-    q = x / scale;
-  }
-  float v = q + zp;
-#else
-  (void)rscale;
-  float v = x / scale + zp;
-#endif
-  v = (255.0f < v) ? 255.0f : v;  // std::min(v, 255.0f)
-  v = (0.0f < v) ? v : 0.0f;      // std::max(0.0f, v)
-  return (int)(uint8_t)roundf(v) - 128;
-}
-
 // One wave per output row.  Plain mode: out row r = quantized X row
 // (row_map[r] or r), width bytes, zero padded to ldq.  Spliced mode (nseg >
 // 1 or width % 64): out row r = concat over segments s of quantized
@@ -205,8 +166,7 @@ __device__ __forceinline__ void quantize_row(const float *__restrict__ x, int ld
                                              int32_t *__restrict__ rowsum, int r, int lane) {
   int8_t *o = q + (int64_t)r * ldq;
   int32_t s = 0;
-  float rs = CATEARS_I8_QDIV ? 1.0f / scale : 0.0f;
-  if (__builtin_isinf(rs) || __builtin_isnan(rs)) rs = 0.0f;
+  const float rs = qbyte_rscale(scale);
   const bool vec = (width & 3) == 0 && (ldx & 3) == 0;
   for (int seg = 0; seg < nseg; ++seg) {
     int src = r + so.off[seg];
@@ -230,8 +190,7 @@ __device__ __forceinline__ void quantize_row(const float *__restrict__ x, int ld
           const int b0 = qbyte(v[j].x, scale, zp, rs), b1 = qbyte(v[j].y, scale, zp, rs);
           const int b2 = qbyte(v[j].z, scale, zp, rs), b3 = qbyte(v[j].w, scale, zp, rs);
           s += b0 + b1 + b2 + b3;
-          const uint32_t packed = (uint32_t)(uint8_t)b0 | ((uint32_t)(uint8_t)b1 << 8) |
-                                  ((uint32_t)(uint8_t)b2 << 16) | ((uint32_t)(uint8_t)b3 << 24);
+          const uint32_t packed = i8_pack4(b0, b1, b2, b3);
           if ((((uintptr_t)(os + c)) & 3) == 0) {
             *reinterpret_cast<uint32_t *>(os + c) = packed;
           } else {
@@ -320,8 +279,7 @@ __device__ __forceinline__ void quantize_rows_fast(const float *__restrict__ x, 
           b[t] = (int)(uint8_t)roundf(w) - 128;
           sum += b[t];
         }
-        const uint32_t packed = (uint32_t)(uint8_t)b[0] | ((uint32_t)(uint8_t)b[1] << 8) |
-                                ((uint32_t)(uint8_t)b[2] << 16) | ((uint32_t)(uint8_t)b[3] << 24);
+        const uint32_t packed = i8_pack4(b[0], b[1], b[2], b[3]);
         *reinterpret_cast<uint32_t *>(os + c) = packed;
       }
     }
@@ -453,24 +411,13 @@ template <int TI, int TJ, int BM, int NT>
 __device__ __forceinline__ void i8_epilogue(const I8Args &p, const i32x16 (&acc)[TI][TJ], int m0, int wrow, int col0,
                                             int r, int h, uint32_t *srs) {
   const QP pa = *static_cast<const QP *>(p.pa);
-  const uint32_t ca = (uint32_t)(128 - pa.zp), cb = (uint32_t)(128 - p.w_zp);
-  const uint32_t kterm = (uint32_t)p.k * ca * cb;
-  const float cscale = pa.scale * p.w_scale;  // matrix.cc:404-405
+  const I8Restore rc = i8_restore(pa, p.w_scale, p.w_zp, p.k);
   // cB * row sum of each spliced row of the block, one row per thread, into
   // LDS (the operand buffers are free once every wave is past the loop)
   __syncthreads();
   for (int t = threadIdx.x; t < BM; t += NT) {
     const int row = m0 + t;
-    uint32_t sum = 0;
-#pragma unroll
-    for (int sg = 0; sg < 8; ++sg) {
-      if (sg < p.nseg) {
-        int src = row + p.off[sg];
-        src = src < 0 ? 0 : (src > p.m - 1 ? p.m - 1 : src);
-        sum += (uint32_t)p.rowsum[src];
-      }
-    }
-    srs[t] = cb * sum;
+    srs[t] = rc.cb * i8_spliced_rowsum(p.rowsum, row, p.m, p.nseg, p.off);
     if (p.mm_part) srs[BM + t] = mm_held(p.row_edge, p.m, p.mm_left, p.mm_right, row);
   }
   __syncthreads();
@@ -481,7 +428,7 @@ __device__ __forceinline__ void i8_epilogue(const I8Args &p, const i32x16 (&acc)
     for (int j = 0; j < TJ; ++j) {
       const int col = col0 + j * 32 + r;
       if (col >= p.n) continue;
-      const uint32_t cterm = ca * (uint32_t)p.colsum[col] + kterm;
+      const uint32_t cterm = i8_cterm(rc, p.colsum[col]);
       const float bias = p.bias ? p.bias[col] : 0.0f;
       const float sc = p.bn_scale ? p.bn_scale[col] : 1.0f;
       const float of = p.bn_offset ? p.bn_offset[col] : 0.0f;
@@ -490,10 +437,8 @@ __device__ __forceinline__ void i8_epilogue(const I8Args &p, const i32x16 (&acc)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int lr = wrow + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          const uint32_t v = (uint32_t)acc[i][j][e] + srs[lr] + cterm;
-          float y = (float)(int32_t)v * cscale;
-          y = y + bias;  // +0 when absent: y is never -0 here (int * positive scale)
-          y = apply_post<decltype(M)::value>(y, sc, of, p.post, p.npost);
+          const float y = i8_output<decltype(M)::value>((uint32_t)acc[i][j][e], srs[lr], cterm, rc.cscale, bias, sc, of,
+                                                        p.post, p.npost);
           if (mm && srs[BM + lr]) mm_take(y, mn, mx);
           if (m0 + lr < p.m) p.y[(int64_t)(m0 + lr) * p.ldy + col] = y;
         }
@@ -517,25 +462,14 @@ __device__ __forceinline__ void i8_epilogue_v(const I8Args &p, const i32x16 (&ac
                                               int col0, int r, int h, char *lds) {
   constexpr int NW = NT / 64, SW = TJ * 32 + 8;  // slab row stride, floats
   const QP pa = *static_cast<const QP *>(p.pa);
-  const uint32_t ca = (uint32_t)(128 - pa.zp), cb = (uint32_t)(128 - p.w_zp);
-  const uint32_t kterm = (uint32_t)p.k * ca * cb;
-  const float cscale = pa.scale * p.w_scale;  // matrix.cc:404-405
+  const I8Restore rc = i8_restore(pa, p.w_scale, p.w_zp, p.k);
   uint32_t *srs = reinterpret_cast<uint32_t *>(lds + NW * 32 * SW * 4);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float *slab = reinterpret_cast<float *>(lds) + wave * 32 * SW;
   __syncthreads();
   for (int t = threadIdx.x; t < BM; t += NT) {
     const int row = m0 + t;
-    uint32_t sum = 0;
-#pragma unroll
-    for (int sg = 0; sg < 8; ++sg) {
-      if (sg < p.nseg) {
-        int src = row + p.off[sg];
-        src = src < 0 ? 0 : (src > p.m - 1 ? p.m - 1 : src);
-        sum += (uint32_t)p.rowsum[src];
-      }
-    }
-    srs[t] = cb * sum;
+    srs[t] = rc.cb * i8_spliced_rowsum(p.rowsum, row, p.m, p.nseg, p.off);
   }
   __syncthreads();
   // the next layer's held rows among this wave's 64: bit t = row wrow + t
@@ -551,7 +485,7 @@ __device__ __forceinline__ void i8_epilogue_v(const I8Args &p, const i32x16 (&ac
 #pragma unroll
   for (int j = 0; j < TJ; ++j) {
     const int col = min(col0 + j * 32 + r, p.n - 1);
-    cterm[j] = ca * (uint32_t)p.colsum[col] + kterm;
+    cterm[j] = i8_cterm(rc, p.colsum[col]);
     bias[j] = p.bias ? p.bias[col] : 0.0f;
     sc[j] = p.bn_scale ? p.bn_scale[col] : 1.0f;
     of[j] = p.bn_offset ? p.bn_offset[col] : 0.0f;
@@ -571,10 +505,8 @@ __device__ __forceinline__ void i8_epilogue_v(const I8Args &p, const i32x16 (&ac
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int rr = (e & 3) + 8 * (e >> 2) + 4 * h;  // row within the slab
-          const uint32_t v = (uint32_t)acc[i][j][e] + srs[wrow + i * 32 + rr] + cterm[j];
-          float y = (float)(int32_t)v * cscale;
-          y = y + bias[j];  // +0 when absent: y is never -0 here (int * positive scale)
-          y = apply_post<decltype(M)::value>(y, sc[j], of[j], p.post, p.npost);
+          const float y = i8_output<decltype(M)::value>((uint32_t)acc[i][j][e], srs[wrow + i * 32 + rr], cterm[j],
+                                                        rc.cscale, bias[j], sc[j], of[j], p.post, p.npost);
           rmx[e] = fmaxf(rmx[e], y);
           rmn[e] = fminf(rmn[e], y);
           slab[rr * SW + j * 32 + r] = y;
@@ -609,12 +541,6 @@ __device__ __forceinline__ void i8_epilogue_v(const I8Args &p, const i32x16 (&ac
   if (mm) mm_store<NT>(p.mm_part, mm2.x, mm2.y);
 }
 
-// Sum of the four signed bytes of a word.
-__device__ __forceinline__ int byte_sum(int w) {
-  const uint32_t u = (uint32_t)w;
-  return ((int)(u << 24) >> 24) + ((int)(u << 16) >> 24) + ((int)(u << 8) >> 24) + (w >> 24);
-}
-
 // Fused requantize (static int8): y exactly as i8_epilogue_v forms it, then
 // Quantize with the NEXT layer's frozen parameters (qbyte's arithmetic, the
 // function the quantize passes use: the same bytes), staged through the wave's LDS slab
@@ -632,28 +558,16 @@ __device__ __forceinline__ void i8_epilogue_q(const I8Args &p, const i32x16 (&ac
   static_assert(C16 == 4 && (32 * C16) % 64 == 0, "four lanes per row chunk group");
   const QP pa = *static_cast<const QP *>(p.pa);
   const QP pn = *static_cast<const QP *>(p.q_qp);
-  const uint32_t ca = (uint32_t)(128 - pa.zp), cb = (uint32_t)(128 - p.w_zp);
-  const uint32_t kterm = (uint32_t)p.k * ca * cb;
-  const float cscale = pa.scale * p.w_scale;  // matrix.cc:404-405
+  const I8Restore rc = i8_restore(pa, p.w_scale, p.w_zp, p.k);
   const float nzp = (float)pn.zp;
-  float nrs = CATEARS_I8_QDIV ? 1.0f / pn.scale : 0.0f;  // as quantize_row
-  if (__builtin_isinf(nrs) || __builtin_isnan(nrs)) nrs = 0.0f;
+  const float nrs = qbyte_rscale(pn.scale);  // as quantize_row
   uint32_t *srs = reinterpret_cast<uint32_t *>(lds + NW * 32 * SB);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int8_t *slab = reinterpret_cast<int8_t *>(lds) + wave * 32 * SB;
   __syncthreads();
   for (int t = threadIdx.x; t < BM; t += NT) {
     const int row = m0 + t;
-    uint32_t sum = 0;
-#pragma unroll
-    for (int sg = 0; sg < 8; ++sg) {
-      if (sg < p.nseg) {
-        int src = row + p.off[sg];
-        src = src < 0 ? 0 : (src > p.m - 1 ? p.m - 1 : src);
-        sum += (uint32_t)p.rowsum[src];
-      }
-    }
-    srs[t] = cb * sum;
+    srs[t] = rc.cb * i8_spliced_rowsum(p.rowsum, row, p.m, p.nseg, p.off);
     if (first_col_tile && p.q_zero && row < p.m) p.q_zero[row] = 0;
   }
   __syncthreads();
@@ -662,7 +576,7 @@ __device__ __forceinline__ void i8_epilogue_q(const I8Args &p, const i32x16 (&ac
 #pragma unroll
   for (int j = 0; j < TJ; ++j) {
     const int col = col0 + j * 32 + r;  // n % 128 == 0: every column exists
-    cterm[j] = ca * (uint32_t)p.colsum[col] + kterm;
+    cterm[j] = i8_cterm(rc, p.colsum[col]);
     bias[j] = p.bias ? p.bias[col] : 0.0f;
     sc[j] = p.bn_scale ? p.bn_scale[col] : 1.0f;
     of[j] = p.bn_offset ? p.bn_offset[col] : 0.0f;
@@ -680,10 +594,8 @@ __device__ __forceinline__ void i8_epilogue_q(const I8Args &p, const i32x16 (&ac
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int rr = (e & 3) + 8 * (e >> 2) + 4 * h;  // row within the slab
-          const uint32_t v = (uint32_t)acc[i][j][e] + srs[wrow + i * 32 + rr] + cterm[j];
-          float y = (float)(int32_t)v * cscale;
-          y = y + bias[j];
-          y = apply_post<decltype(M)::value>(y, sc[j], of[j], p.post, p.npost);
+          const float y = i8_output<decltype(M)::value>((uint32_t)acc[i][j][e], srs[wrow + i * 32 + rr], cterm[j],
+                                                        rc.cscale, bias[j], sc[j], of[j], p.post, p.npost);
           const float q0 = y * nrs;
           const float qq = __builtin_fmaf(__builtin_fmaf(-pn.scale, q0, y), nrs, q0);
           bad |= __builtin_isinf(qq) || __builtin_isnan(qq);
@@ -713,12 +625,8 @@ __device__ __forceinline__ void i8_epilogue_q(const I8Args &p, const i32x16 (&ac
         const int row = m0 + wrow + i * 32 + rr;
         const i32x4 v = *reinterpret_cast<const i32x4 *>(slab + rr * SB + 16 * c);
         int sum = byte_sum(v[0]) + byte_sum(v[1]) + byte_sum(v[2]) + byte_sum(v[3]);
-        sum += __shfl_xor(sum, 1, 64);
-        sum += __shfl_xor(sum, 2, 64);
-        if (row < p.m) {
-          *reinterpret_cast<i32x4 *>(p.qy + (int64_t)row * p.n + col0 + 16 * c) = v;
-          if (c == 0) atomicAdd(p.q_rowsum + row, sum);
-        }
+        if (row < p.m) *reinterpret_cast<i32x4 *>(p.qy + (int64_t)row * p.n + col0 + 16 * c) = v;
+        i8_rowsum_group_add<C16>(sum, row < p.m, p.q_rowsum + min(row, p.m - 1));  // lane c == 0 adds
       }
       wave_lds_sync();
     }

@@ -180,6 +180,22 @@ int Config::integer(const std::string &key, int *v) const {
   return CE_GPU_OK;
 }
 
+int read_int8_ranges(const Config &cf, std::vector<float> *ranges, std::string *path) {
+  ranges->clear();
+  path->clear();
+  if (!cf.kv.count("gpu_int8_ranges")) return CE_GPU_OK;
+  MIO_TRY(cf.path("gpu_int8_ranges", path));
+  Reader rd;
+  MIO_TRY(rd.open(*path));
+  MIO_TRY(rd.vec(ranges));
+  if (ranges->empty() || ranges->size() % 2 != 0) {
+    const size_t n = ranges->size();
+    ranges->clear();
+    return fail(CE_GPU_EINVAL, *path + fmt(": model_quantize_static: %zu floats are not (min, max) pairs", n));
+  }
+  return CE_GPU_OK;
+}
+
 // ------------------------------------------------------------------ NN02 --
 
 int read_nnet(Reader &rd, std::vector<RawLayer> *layers, int *hl, int *hr) {

@@ -72,6 +72,13 @@ struct Config {
   int integer(const std::string &key, int *v) const;
 };
 
+// The configuration key gpu_int8_ranges = <path> (this implementation's own;
+// resolved like nnet / prior): a VEC0 of min0 max0 min1 max1 ..., the
+// h_ranges of ce_gpu_model_quantize_static.  Key absent: *ranges empty, OK.
+// A file that is not a non-empty list of pairs fails with CE_GPU_EINVAL and
+// the file name in the message; *path receives the resolved file name.
+int read_int8_ranges(const Config &cf, std::vector<float> *ranges, std::string *path);
+
 // Layer ids (src/nnet.h:21-30).
 enum LayerId { kLinear = 0, kReLU = 1, kNormalize = 2, kSoftmax = 3, kSplice = 6, kBatchNorm = 7,
                kLogSoftmax = 8, kNarrow = 9 };

@@ -37,6 +37,7 @@ ABI = [
     "ce_gpu_sessions_push_s16", "ce_gpu_debug_counters",
     "ce_gpu_quant_params_from_range", "ce_gpu_model_calibrate", "ce_gpu_model_quantize_static",
     "ce_gpu_model_quant_params",
+    "ce_gpu_i8_latency_plan", "ce_gpu_debug_i8_latency_launches",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -124,6 +125,8 @@ def lib():
         "ce_gpu_model_calibrate": (ci, [vp, vp, vp, vp, ci, vp]),
         "ce_gpu_model_quantize_static": (ci, [vp, vp, vp, ci]),
         "ce_gpu_model_quant_params": (ci, [vp, vp, vp, ci, pi]),
+        "ce_gpu_i8_latency_plan": (ci, [ci, ci, ci, pi, pi]),
+        "ce_gpu_debug_i8_latency_launches": (ci, [pi64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -169,7 +172,9 @@ class Context:
 
     def set_latency(self, on=True):
         """Latency mode (ce_gpu_ctx_set_latency): split-K nnet GEMMs for small
-        row blocks scored one at a time."""
+        row blocks scored one at a time.  Static int8 models take their
+        split-K pair up to the crossover of i8_latency_plan (the same bits as
+        off); dynamic int8 ignores the mode."""
         check(lib().ce_gpu_ctx_set_latency(self.h, int(bool(on))))
 
     FBANK_MODES = {"exact": 0, "fast": 1}
@@ -457,6 +462,23 @@ def debug_counters():
     a, f = ctypes.c_int64(), ctypes.c_int64()
     check(lib().ce_gpu_debug_counters(ctypes.byref(a), ctypes.byref(f)))
     return a.value, f.value
+
+
+def i8_latency_plan(kpad, n, rows):
+    """ce_gpu_i8_latency_plan: (slices, k_steps_per_slice) of a static int8
+    Linear (K padded to kpad bytes, n outputs) on `rows` rows in latency
+    mode; slices == 0 means the throughput kernel.  Needs no device."""
+    s, per = ctypes.c_int(), ctypes.c_int()
+    check(lib().ce_gpu_i8_latency_plan(int(kpad), int(n), int(rows), ctypes.byref(s), ctypes.byref(per)))
+    return s.value, per.value
+
+
+def debug_i8_latency_launches():
+    """ce_gpu_debug_i8_latency_launches: split-K int8 GEMM launches of this
+    process so far."""
+    n = ctypes.c_int64()
+    check(lib().ce_gpu_debug_i8_latency_launches(ctypes.byref(n)))
+    return n.value
 
 
 class Sessions:

@@ -95,6 +95,30 @@ Status AcousticModel::Read(const Configuration &conf) {
   if (rc != CE_GPU_OK) return Status::Corruption(util::Format("{}: {}", nnet_file, ce_gpu_last_error()));
   int pdfs = 0;
   ce_gpu_model_info(model_, nullptr, nullptr, &feat_dim_, &pdfs, nullptr, nullptr);
+  // gpu_int8_ranges = <path>: calibrated static int8.  The file is a VEC0 of
+  // min0 max0 min1 max1 ... (one pair per Linear, e.g. what
+  // ce_gpu_model_calibrate returned); its rows do not depend on the batch, so
+  // gpu_latency_mode and gpu_batch_streams work as on the fp32 model.
+  const std::string ranges_file = conf.GetPathOrElse("gpu_int8_ranges", "");
+  if (!ranges_file.empty()) {
+    Vector<float> ranges;
+    {
+      util::ReadableFile fd;
+      PK_CHECK_STATUS(fd.Open(ranges_file));
+      PK_CHECK_STATUS(ranges.Read(&fd));
+    }
+    const int rc8 = ranges.Dim() == 0 || ranges.Dim() % 2 != 0
+                        ? CE_GPU_EINVAL
+                        : ce_gpu_model_quantize_static(rt.ctx(), model_, ranges.Data(), ranges.Dim() / 2);
+    if (rc8 != CE_GPU_OK) {
+      const std::string why = ranges.Dim() == 0 || ranges.Dim() % 2 != 0
+                                  ? util::Format("{} floats are not (min, max) pairs", ranges.Dim())
+                                  : std::string(ce_gpu_last_error());
+      ce_gpu_model_destroy(model_);
+      model_ = nullptr;
+      return Status::Corruption(util::Format("{}: {}", ranges_file, why));
+    }
+  }
   // streaming chunks are small row blocks: latency mode (split-K GEMMs,
   // ce_gpu_ctx_set_latency) unless the config turns it off.  The flag is this
   // model's: RunBlocks sets it on the shared context for each of its calls,

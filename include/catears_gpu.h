@@ -66,7 +66,9 @@ const char *ce_gpu_last_error(void);
  * library; 0.6 adds the device-resident sessions (ce_gpu_sessions_*) and
  * ce_gpu_debug_counters; 0.7 adds calibrated static int8
  * (ce_gpu_quant_params_from_range, ce_gpu_model_calibrate,
- * ce_gpu_model_quantize_static, ce_gpu_model_quant_params). */
+ * ce_gpu_model_quantize_static, ce_gpu_model_quant_params); the latency mode
+ * of static int8 (ce_gpu_i8_latency_plan, ce_gpu_debug_i8_latency_launches,
+ * the config key gpu_int8_ranges) only adds to 0.7. */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -107,8 +109,27 @@ int ce_gpu_ctx_overflow(ce_gpu_ctx *ctx, int *overflow);
  * order.  Measured on MI355X (TDNN-S, one stream): 92 us per 70-row chunk
  * (761 us in the default mode), 390 us per 1018-row utterance (780 us);
  * past ~2000 rows the default mode is faster.  Off (0, the default) is the
- * throughput mode for full 4096-row batches. */
+ * throughput mode for full 4096-row batches.
+ *   Static int8 models (ce_gpu_model_quantize_static): on, a Linear whose row
+ * block is at most the measured crossover (ce_gpu_i8_latency_plan returns
+ * slices > 0) runs as a split-K pair as well -- int32 slice partials, then a
+ * reduce that restores the zero points and writes fp32 or the next layer's
+ * bytes.  The accumulators are integers modulo 2^32, so the rows are the
+ * bits of the mode off for every split; larger blocks take the throughput
+ * kernel automatically, and a caller may leave the mode on for any batch.
+ *   Dynamic int8 models (ce_gpu_model_quantize) ignore the mode: their
+ * parameters need a reduction over the block first. */
 int ce_gpu_ctx_set_latency(ce_gpu_ctx *ctx, int on);
+
+/* The slice rule of the static int8 latency mode, on the host (no device,
+ * like ce_gpu_quant_params_from_range): a Linear of `kpad` K-bytes (its K
+ * padded to 128) and `n` outputs scored on `rows` rows runs as *slices
+ * K-slices of *k_steps_per_slice 64-byte steps each (the last one may hold
+ * fewer, never none), about one block per CU.  *slices = 0: the throughput
+ * kernel (rows above the crossover, or kpad not a multiple of 128).  The rule
+ * may depend on rows because the bits do not.  CE_GPU_EINVAL for a NULL
+ * pointer or a non-positive argument. */
+int ce_gpu_i8_latency_plan(int kpad, int n, int rows, int *slices, int *k_steps_per_slice);
 
 /* Tile shape of ctx's throughput-mode bf16x6 GEMMs (round 5): on (1), every
  * layer runs the direct-weight kernel on 128 x 128 tiles -- twice the blocks
@@ -186,6 +207,10 @@ int ce_gpu_trace_mark(int device, void *stream, int tag);
  * allocated nothing.  Either pointer may be NULL.  Measurement plumbing; no
  * reference counterpart. */
 int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees);
+/* Process-wide count of the static int8 latency GEMM's launches
+ * (i8_lat_gemm_kernel; counted on the host when one is enqueued): shows which
+ * of the two int8 kernels a call took.  Measurement plumbing as above. */
+int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
 
 /* -------------------------------------------------------------- model --- */
 
@@ -194,6 +219,12 @@ int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees);
  * relative paths resolved against the config's directory,
  * src/configuration.cc:52-66), the NN02 nnet (src/nnet.cc:221-293), the VEC0
  * prior (then log, src/am.cc:41-44) and the tid2pdf map; uploads weights.
+ * One key of this implementation's own: gpu_int8_ranges = <path> (resolved
+ * like nnet / prior) names a VEC0 of 2 * num_linear floats min0 max0 min1
+ * max1 ... (ce_gpu_model_quantize_static's h_ranges, e.g. what
+ * ce_gpu_model_calibrate returned); the loaded model is then switched with
+ * ce_gpu_model_quantize_static.  A wrong count or a bad range fails with
+ * that call's CE_GPU_EINVAL text prefixed with the file name.
  * Fails with CE_GPU_ENOTSUP for a topology whose whole-utterance result
  * would differ from the reference's chunked one. */
 int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_model **out);

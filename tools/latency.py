@@ -3,7 +3,13 @@ to back, HIP events), default (throughput) mode vs latency mode
 (ce_gpu_ctx_set_latency): the streaming AcousticModel chunk (chunk_size 50 +
 20 context rows), a 250-frame chunk, one 10 s utterance (1018 rows) and the
 bench's 4072-row batch.   python tools/latency.py [calls]
-(LAT_MODES=latency LAT_ROWS=70 restrict the modes and row counts)"""
+(LAT_MODES=latency LAT_ROWS=70 restrict the modes and row counts)
+
+  python tools/latency.py --static-int8 [calls]
+      the static int8 leg (ce_gpu_model_quantize_static, calibrated on 12 s of
+      the synthetic audio): the 70-row chunk per call (LAT_ROWS for a sweep)
+      with latency mode off and on, beside the bf16x6 latency mode, see
+      static_int8()"""
 import hashlib
 import json
 import os
@@ -85,5 +91,74 @@ def main(calls=200):
     print(json.dumps(res))
 
 
+def per_call_us(fn, calls):
+    """Event-bracketed device time of each of `calls` back-to-back calls."""
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+    torch.cuda.synchronize()
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return np.array([a.elapsed_time(b) * 1e3 for a, b in ev])
+
+
+def static_int8(calls=200):
+    """TDNN-S as static int8, one nnet_propagate per call: latency mode off
+    (the throughput int8 kernel) and on (the split-K pair up to the crossover
+    of ce_gpu_i8_latency_plan), and the bf16x6 latency mode of the fp32 model
+    in the same run.  Per leg and row count: the median and the 10th / 90th
+    percentile of the per-call device times, the mean of the calls back to
+    back, and the output digest (off and on must agree).  The legs alternate
+    off / on / bf16x6 / on / off, so each int8 leg is measured twice."""
+    mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
+    conf = synth.write_model(mdir, "tdnn-s")
+    sizes = [int(v) for v in os.environ.get("LAT_ROWS", "70").split(",")]
+    ctxs = {"off": gpu.Context(0), "on": gpu.Context(0), "bf16x6": gpu.Context(0)}
+    ctxs["on"].set_latency(True)
+    ctxs["bf16x6"].set_latency(True)
+    cal = [synth.pcm(2900 + i, 48000) for i in range(4)]
+    m0 = gpu.Model(ctxs["off"], conf)
+    plan = gpu.Plan(ctxs["off"], [len(w) for w in cal], m0)
+    ranges = m0.calibrate(ctxs["off"], plan, gpu.fbank(ctxs["off"], plan, torch.from_numpy(np.concatenate(cal)).cuda()))
+    models = {"off": m0.quantize_static(ctxs["off"], ranges),
+              "on": gpu.Model(ctxs["on"], conf).quantize_static(ctxs["on"], ranges),
+              "bf16x6": gpu.Model(ctxs["bf16x6"], conf)}
+    # absent from libraries older than the int8 latency mode (A/B runs)
+    launches = getattr(gpu, "debug_i8_latency_launches", lambda: 0)
+    res = {"version": gpu.lib().ce_gpu_version().decode(), "device": torch.cuda.get_device_name(0), "calls": calls}
+    for rows in sizes:
+        x = torch.from_numpy(np.random.default_rng(rows).normal(9, 3, size=(rows, 40)).astype(np.float32)).cuda()
+        for i, leg in enumerate(["off", "on", "bf16x6", "on", "off"]):
+            ctx, model = ctxs[leg], models[leg]
+            out = gpu.nnet_propagate(ctx, model, x)
+            for _ in range(20):
+                gpu.nnet_propagate(ctx, model, x, out=out)
+            n0 = launches()
+            us = per_call_us(lambda: gpu.nnet_propagate(ctx, model, x, out=out), calls)
+            n1 = launches()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                gpu.nnet_propagate(ctx, model, x, out=out)
+            b.record()
+            torch.cuda.synchronize()
+            digest = hashlib.sha1(out.cpu().numpy().tobytes()).hexdigest()[:12]
+            name = "bf16x6_latency" if leg == "bf16x6" else f"static_int8_latency_{leg}"
+            rec = {"p50_us": round(float(np.percentile(us, 50)), 1), "p10_us": round(float(np.percentile(us, 10)), 1),
+                   "p90_us": round(float(np.percentile(us, 90)), 1),
+                   "back_to_back_us": round(a.elapsed_time(b) * 1e3 / calls, 1), "sha1": digest,
+                   "i8_latency_gemms_per_call": (n1 - n0) / calls}
+            res[f"{name}/{rows}/run{i}"] = rec
+            print(f"{name:24s} rows {rows:5d}: p50 {rec['p50_us']:7.1f} us  [{rec['p10_us']:.1f}, {rec['p90_us']:.1f}]"
+                  f"  back to back {rec['back_to_back_us']:7.1f} us  split-K GEMMs/call {rec['i8_latency_gemms_per_call']:.0f}"
+                  f"  out {digest}", flush=True)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 200)
+    nums = [int(v) for v in sys.argv[1:] if not v.startswith("--")]
+    if "--static-int8" in sys.argv[1:]:
+        static_int8(*nums[:1])
+    else:
+        main(*nums[:1])

@@ -17,7 +17,8 @@ Both legs compute the same rows (checked once per N, bit for bit).
   python tools/session_latency.py [ticks] [rounds]      -> JSON lines
   python tools/session_latency.py --static-int8 [ticks] [rounds]
       the 64-stream push only: the bf16x6 latency-mode model beside a static
-      int8 model (ce_gpu_model_quantize_static), see static_int8()"""
+      int8 model (ce_gpu_model_quantize_static) on a throughput context and
+      on a latency-mode context, see static_int8()"""
 import json
 import os
 import sys
@@ -136,8 +137,12 @@ def main(ticks=100, rounds=3):
 
 def static_int8(ticks=100, rounds=3, n=64):
     """The n-stream push with a static int8 model (calibrated on 12 s of the
-    synthetic audio, no CMVN) beside the bf16x6 latency-mode push of main():
-    two contexts, one session set each, alternating blocks of `ticks` ticks."""
+    synthetic audio, no CMVN) beside the bf16x6 latency-mode push of main(),
+    and the same static int8 model on a latency-mode context (the split-K
+    int8 pair where the slice rule gives it the push's row count, the
+    throughput kernel above the crossover: same rows, checked on the last
+    tick): three contexts, one session set each, alternating blocks of
+    `ticks` ticks."""
     mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
     conf = synth.write_model(mdir, "tdnn-s")
     ctx_x6 = gpu.Context(0)
@@ -148,31 +153,41 @@ def static_int8(ticks=100, rounds=3, n=64):
     plan = gpu.Plan(ctx_i8, [len(w) for w in cal], m_i8)
     ranges = m_i8.calibrate(ctx_i8, plan, gpu.fbank(ctx_i8, plan, torch.from_numpy(np.concatenate(cal)).cuda()))
     m_i8.quantize_static(ctx_i8, ranges)
+    ctx_i8l = gpu.Context(0)
+    ctx_i8l.set_latency(True)
+    m_i8l = gpu.Model(ctx_i8l, conf).quantize_static(ctx_i8l, ranges)
     print(json.dumps({"device": torch.cuda.get_device_name(0), "model": "tdnn-s", "chunk_samples": CHUNK,
-                      "slots": n, "ticks": ticks, "rounds": rounds, "legs": ["bf16x6 latency", "static int8"],
+                      "slots": n, "ticks": ticks, "rounds": rounds, "legs": ["bf16x6 latency", "static int8", "static int8 latency"],
                       "version": gpu.lib().ce_gpu_version().decode()}), flush=True)
     total = CHUNK * ticks * (rounds + 1)
     waves = [synth.pcm(3000 + s, total) for s in range(n)]
-    legs = [(ctx_x6, gpu.Sessions(ctx_x6, m_x6, n, CHUNK)), (ctx_i8, gpu.Sessions(ctx_i8, m_i8, n, CHUNK))]
+    legs = [(ctx_x6, gpu.Sessions(ctx_x6, m_x6, n, CHUNK)), (ctx_i8, gpu.Sessions(ctx_i8, m_i8, n, CHUNK)),
+            (ctx_i8l, gpu.Sessions(ctx_i8l, m_i8l, n, CHUNK))]
     out = torch.empty((n * 16, m_x6.num_pdfs), dtype=torch.float32, device="cuda")
-    slots, times = list(range(n)), ([], [])
+    slots, times = list(range(n)), ([], [], [])
     counters = None
+    last = [None, None, None]
+    lat0 = gpu.debug_i8_latency_launches()
     for r in range(rounds + 1):
         for k, (ctx, sess) in enumerate(legs):
             for t in range(r * ticks, (r + 1) * ticks):
                 pcm = np.concatenate([w[t * CHUNK:(t + 1) * CHUNK] for w in waves])
                 t0 = time.perf_counter()
-                sess.push(slots, torch.from_numpy(pcm).cuda(), [CHUNK] * n, out=out)
+                o, _ = sess.push(slots, torch.from_numpy(pcm).cuda(), [CHUNK] * n, out=out)
                 ctx.synchronize()
                 if r:  # block 0 is the warm-up
                     times[k].append(time.perf_counter() - t0)
+            last[k] = o.cpu().numpy().copy()
         if r == 0:
             counters = gpu.debug_counters()
-    rec = {"slots": n, "timed_ticks": len(times[0]), "pushes_allocated_nothing": gpu.debug_counters() == counters}
-    for name, v in (("bf16x6_latency", times[0]), ("static_int8", times[1])):
+    rec = {"slots": n, "timed_ticks": len(times[0]), "pushes_allocated_nothing": gpu.debug_counters() == counters,
+           "static_int8_rows_identical": bool(np.array_equal(last[1].view(np.uint32), last[2].view(np.uint32))),
+           "i8_latency_gemm_launches": gpu.debug_i8_latency_launches() - lat0}
+    for name, v in (("bf16x6_latency", times[0]), ("static_int8", times[1]), ("static_int8_latency", times[2])):
         rec[name] = {"median_us": round(pct(v, 50) * 1e6, 1), "p10_us": round(pct(v, 10) * 1e6, 1),
                      "p90_us": round(pct(v, 90) * 1e6, 1)}
     rec["static_int8_over_bf16x6"] = round(pct(times[1], 50) / pct(times[0], 50), 2)
+    rec["static_int8_latency_over_static_int8"] = round(pct(times[2], 50) / pct(times[1], 50), 2)
     print(json.dumps(rec), flush=True)
     for _, sess in legs:
         sess.close()
