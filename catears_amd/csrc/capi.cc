@@ -200,11 +200,11 @@ int knob_env(const char *name, int dflt) {
 
 // Default matrix-core form of the fp32 program: bf16x6.  Another mode is a
 // per-model choice through ce_gpu_model_set_gemm; the experiments library
-// also takes CATEARS_NNET_GEMM (0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p, the
-// ce_gpu_model_set_gemm numbers) for the tools.
+// also takes CATEARS_NNET_GEMM (0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p, 4 bf16,
+// the ce_gpu_model_set_gemm numbers) for the tools.
 static int default_gemm() {
   static const int g = CE_KNOB("CATEARS_NNET_GEMM", (int)CE_GPU_GEMM_BF16X6);
-  return g >= CE_GPU_GEMM_FP32 && g <= CE_GPU_GEMM_BF16X6_PLANES ? g : -1;
+  return g >= CE_GPU_GEMM_FP32 && g <= CE_GPU_GEMM_BF16 ? g : -1;
 }
 
 static int build_program(const std::vector<RawLayer> &layers, int left, int right, ce_gpu_model *m) {
@@ -345,9 +345,10 @@ static int build_program(const std::vector<RawLayer> &layers, int left, int righ
   }
   m->x3_ok = m->x3_ok && m->x6_ok;
   const int want = default_gemm();
-  if (want < 0) return fail(CE_GPU_EINVAL, "default GEMM mode: not one of 0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p");
+  if (want < 0) return fail(CE_GPU_EINVAL, "default GEMM mode: not one of 0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p, 4 bf16");
   m->gemm = want == CE_GPU_GEMM_F16X3 && m->x3_ok   ? CE_GPU_GEMM_F16X3
             : want == CE_GPU_GEMM_BF16X6_PLANES && m->x6_ok ? CE_GPU_GEMM_BF16X6_PLANES
+            : want == CE_GPU_GEMM_BF16 && m->x6_ok ? CE_GPU_GEMM_BF16
             : want != CE_GPU_GEMM_FP32 && m->x6_ok ? CE_GPU_GEMM_BF16X6
                                                     : CE_GPU_GEMM_FP32;
   return CE_GPU_OK;
@@ -693,11 +694,18 @@ int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_mo
   CE_TRY(cf.integer("chunk_size", &chunk));
   CE_TRY(cf.integer("num_pdfs", &num_pdfs));
   CE_TRY(cf.path("tid2pdf", &tid2pdf));
+  // gpu_gemm: the GEMM mode from the config; a bad name fails before any upload
+  int gemm = -1;
+  CE_TRY(read_gpu_gemm(cf, &gemm));
   ce_gpu_model *m = nullptr;
   CE_TRY(load_model(ctx, nnet, prior, left, right, tid2pdf, &m));
   m->chunk = chunk;
-  // gpu_int8_ranges: static int8 from the config (model_io.cc)
   std::unique_ptr<ce_gpu_model> own(m);
+  if (gemm >= 0) {
+    const int rc = ce_gpu_model_set_gemm(m, gemm);
+    if (rc != CE_GPU_OK) return fail(rc, cf.file + ": gpu_gemm = " + cf.kv["gpu_gemm"] + ": " + last_error());
+  }
+  // gpu_int8_ranges: static int8 from the config (model_io.cc)
   std::string ranges_path;
   std::vector<float> ranges;
   CE_TRY(read_int8_ranges(cf, &ranges, &ranges_path));
@@ -725,7 +733,7 @@ int ce_gpu_model_info(const ce_gpu_model *m, int *left_context, int *right_conte
 int ce_gpu_model_set_gemm(ce_gpu_model *m, int mode) {
   if (!m) return fail(CE_GPU_EINVAL, "NULL model");
   if (mode != CE_GPU_GEMM_FP32 && mode != CE_GPU_GEMM_BF16X6 && mode != CE_GPU_GEMM_F16X3 &&
-      mode != CE_GPU_GEMM_BF16X6_PLANES)
+      mode != CE_GPU_GEMM_BF16X6_PLANES && mode != CE_GPU_GEMM_BF16)
     return fail(CE_GPU_EINVAL, "unknown GEMM mode");
   if (mode != CE_GPU_GEMM_FP32 && !m->x6_ok)
     return fail(CE_GPU_ENOTSUP, "this nnet program cannot run on split planes (unfused row op or widths)");
@@ -738,6 +746,12 @@ int ce_gpu_model_set_gemm(ce_gpu_model *m, int mode) {
 int ce_gpu_model_get_gemm(const ce_gpu_model *m, int *mode) {
   if (!m || !mode) return fail(CE_GPU_EINVAL, "NULL argument");
   *mode = m->gemm;
+  return CE_GPU_OK;
+}
+
+int ce_gpu_gemm_mode_from_name(const char *name, int *mode) {
+  if (!name || !mode) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (!gemm_mode_from_name(name, mode)) return fail(CE_GPU_EINVAL, std::string("unknown GEMM mode name: ") + name);
   return CE_GPU_OK;
 }
 
@@ -1230,6 +1244,77 @@ static int run_steps_x6(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, 
   return CE_GPU_OK;
 }
 
+// The plain bf16 program (kernels/gemm_bf16.hip, CE_GPU_GEMM_BF16): the first
+// layer's spliced block is written as bf16, every hidden layer's epilogue
+// writes bf16(y) for the next, the last layer writes fp32.  Two ping-pong
+// blocks of rows x max_in bf16 plus the fp32 output: a third of
+// run_steps_x6's planes, so inside what reserve_packed_rows reserves (its
+// max_in rounds widths up to 64, this one to 32) and a session push still
+// allocates nothing.  The context's latency and wide-tile settings are not
+// read: one kernel family, its tile a function of (rows, n).
+static int run_steps_bf16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
+                          const int *row_map, const float **y, int *ldy) {
+  int max_in = 0;
+  for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
+  for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
+  const size_t blk_floats = ((size_t)rows * max_in + 1) / 2;
+  const size_t blk_stride = (blk_floats + 63) / 64 * 64;
+  CE_TRY(ensure_workspace(ctx, 2 * blk_stride + (size_t)rows * m->num_pdfs));
+  uint16_t *sbuf[2] = {reinterpret_cast<uint16_t *>(ctx->workspace.as<float>()),
+                       reinterpret_cast<uint16_t *>(ctx->workspace.as<float>() + blk_stride)};
+  float *out = ctx->workspace.as<float>() + 2 * blk_stride;
+  const uint16_t *xs = nullptr;
+  int px = 0, cur = 0;
+  for (size_t i = 0; i < m->steps.size(); ++i) {
+    const GemmLayer &g = m->steps[i].gemm;
+    const bool last = i + 1 == m->steps.size();
+    X6Gemm a;
+    if (i == 0) {
+      ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
+      CE_TRY(launch_splice_pad_bf16(ctx->stream, x, ldx, rows, g.din, g.nseg, g.off, row_map, sbuf[cur], g.kpad));
+      xs = sbuf[cur];
+      px = g.kpad;
+      cur ^= 1;
+      a.din = g.kpad;
+      a.nseg = 1;
+    } else {
+      a.din = g.din;
+      a.nseg = g.nseg;
+      for (int s = 0; s < 8; ++s) a.off[s] = g.off[s];
+    }
+    a.x = xs;
+    a.ldx = px;
+    a.wd = g.wdir.as<uint16_t>();
+    a.wd_kt = g.kpad / 32;
+    a.m = rows;
+    a.n = g.n;
+    a.kpad = i == 0 ? g.kpad : g.nseg * g.din;
+    a.bias = g.bias.as<float>();
+    a.bn_scale = g.bn_scale.as<float>();
+    a.bn_offset = g.bn_offset.as<float>();
+    for (int q = 0; q < 4; ++q) a.post[q] = g.post[q];
+    a.npost = g.npost;
+    const int pn = (g.n + 31) / 32 * 32;
+    if (last) {
+      a.y32 = out;
+      a.ldy = g.n;
+    } else {
+      a.y16 = sbuf[cur];
+      a.ldy = pn;
+    }
+    {
+      ProfScope prof(ctx, CE_GPU_PROF_GEMM);
+      CE_TRY(launch_gemm_bf16(ctx->stream, a));
+    }
+    xs = sbuf[cur];
+    px = pn;
+    cur ^= 1;
+  }
+  *y = out;
+  *ldy = m->steps.back().gemm.n;
+  return CE_GPU_OK;
+}
+
 static int ensure_overflow_word(ce_gpu_ctx *ctx) {
   if (ctx->overflow.ptr) return CE_GPU_OK;
   CE_TRY(ctx->overflow.alloc(256));
@@ -1488,6 +1573,7 @@ static int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int
   if (m->int8 && m->int8_static) return run_steps_i8_static(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->int8) return run_steps_i8(ctx, m, x, ldx, rows, row_map, row_edge, y, ldy);
   if (m->gemm == CE_GPU_GEMM_F16X3) return run_steps_x3(ctx, m, x, ldx, rows, row_map, y, ldy);
+  if (m->gemm == CE_GPU_GEMM_BF16) return run_steps_bf16(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->gemm == CE_GPU_GEMM_BF16X6_PLANES) return run_steps_x6(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->gemm == CE_GPU_GEMM_BF16X6)
     return x6_f32in() ? run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail)
@@ -1624,8 +1710,9 @@ int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows) {
     if (g.din % 32 != 0) scratch = std::max(scratch, r * g.kpad * sizeof(float));
   }
   if (m->x6_ok && all_gemm) {
-    // three bf16 planes (1.5 floats per element) cover the fp32 chain and
-    // the two fp16 planes as well
+    // three bf16 planes (1.5 floats per element) cover the fp32 chain, the
+    // two fp16 planes and the plain bf16 mode's single one (run_steps_bf16)
+    // as well
     const size_t blk = (r * max_in * 3 / 2 + 1 + 63) / 64 * 64;
     ws = std::max(ws, 2 * blk + r * m->num_pdfs);
     for (size_t i = 0; i < m->steps.size(); ++i) {

@@ -520,6 +520,20 @@ int launch_lat_finalize(hipStream_t s, const LatTail &t, int first, int rows, bo
 int launch_splice_pad_split(hipStream_t s, const float *in, int ld_in, int rows, int din, int nseg, const int *off,
                             const int *row_map, uint16_t *out, int po);
 
+// Plain bf16 GEMM (kernels/gemm_bf16.hip, CE_GPU_GEMM_BF16): one MFMA product
+// of bf16(x) and plane 0 of the fragment image a.wd (= bf16(w)), fp32
+// accumulation in ascending K.  Of X6Gemm it reads x / ldx (rows of bf16, no
+// planes), wd / wd_kt, the K geometry (din % 32 == 0, nseg * din == kpad),
+// the epilogue fields and y16 (bf16(y), ldy elements per row) or y32.
+int launch_gemm_bf16(hipStream_t s, const X6Gemm &a);
+// Its tile rule, a function of (rows, n) only: true = 32 x 32 tiles, false =
+// 128 x 128.  Same bits either way.
+constexpr int kB16LargeMinTiles = 64;
+bool bf16_small_tile(int rows, int n);
+// splice_pad (below) written as bf16, out row r at out + r * po.
+int launch_splice_pad_bf16(hipStream_t s, const float *in, int ld_in, int rows, int din, int nseg, const int *off,
+                           const int *row_map, uint16_t *out, int po);
+
 // fp32-accurate GEMM on the fp16 matrix cores (kernels/gemm_f16x3.hip):
 // operands as two scaled fp16 planes, three MFMA products; same geometry as
 // X6Gemm with two planes.  unscale = 2^-(weight shift + activation shift);

@@ -196,6 +196,34 @@ int read_int8_ranges(const Config &cf, std::vector<float> *ranges, std::string *
   return CE_GPU_OK;
 }
 
+bool gemm_mode_from_name(const char *name, int *mode) {
+  static const struct {
+    const char *name;
+    int mode;
+  } kModes[] = {{"fp32", CE_GPU_GEMM_FP32},
+                {"bf16x6", CE_GPU_GEMM_BF16X6},
+                {"bf16x6p", CE_GPU_GEMM_BF16X6_PLANES},
+                {"f16x3", CE_GPU_GEMM_F16X3},
+                {"bf16", CE_GPU_GEMM_BF16}};
+  if (!name) return false;
+  for (const auto &m : kModes)
+    if (strcmp(name, m.name) == 0) {
+      *mode = m.mode;
+      return true;
+    }
+  return false;
+}
+
+int read_gpu_gemm(const Config &cf, int *mode) {
+  *mode = -1;
+  auto it = cf.kv.find("gpu_gemm");
+  if (it == cf.kv.end()) return CE_GPU_OK;
+  if (!gemm_mode_from_name(it->second.c_str(), mode))
+    return fail(CE_GPU_EINVAL, cf.file + ": gpu_gemm = " + it->second +
+                                   ": not a GEMM mode (fp32, bf16x6, bf16x6p, f16x3, bf16)");
+  return CE_GPU_OK;
+}
+
 // ------------------------------------------------------------------ NN02 --
 
 int read_nnet(Reader &rd, std::vector<RawLayer> *layers, int *hl, int *hr) {

@@ -79,6 +79,16 @@ struct Config {
 // the file name in the message; *path receives the resolved file name.
 int read_int8_ranges(const Config &cf, std::vector<float> *ranges, std::string *path);
 
+// ce_gpu_gemm_mode_from_name: fp32, bf16x6, bf16x6p, f16x3, bf16 -> the
+// CE_GPU_GEMM_* number; false for any other name (or NULL).
+bool gemm_mode_from_name(const char *name, int *mode);
+
+// The configuration key gpu_gemm = <name> (this implementation's own): the
+// GEMM mode the loaded model is switched to.  Key absent: *mode = -1, OK.  A
+// name gemm_mode_from_name does not know fails with CE_GPU_EINVAL and the key
+// and value in the message.
+int read_gpu_gemm(const Config &cf, int *mode);
+
 // Layer ids (src/nnet.h:21-30).
 enum LayerId { kLinear = 0, kReLU = 1, kNormalize = 2, kSoftmax = 3, kSplice = 6, kBatchNorm = 7,
                kLogSoftmax = 8, kNarrow = 9 };

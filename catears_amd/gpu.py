@@ -38,10 +38,11 @@ ABI = [
     "ce_gpu_quant_params_from_range", "ce_gpu_model_calibrate", "ce_gpu_model_quantize_static",
     "ce_gpu_model_quant_params",
     "ce_gpu_i8_latency_plan", "ce_gpu_debug_i8_latency_launches",
+    "ce_gpu_gemm_mode_from_name",
 ]
 
 # ce_gpu_model_set_gemm modes
-GEMM_MODES = {"fp32": 0, "bf16x6": 1, "f16x3": 2, "bf16x6p": 3}
+GEMM_MODES = {"fp32": 0, "bf16x6": 1, "f16x3": 2, "bf16x6p": 3, "bf16": 4}
 
 _lib = None
 
@@ -109,6 +110,7 @@ def lib():
         "ce_gpu_loglik_columns": (ci, [vp, vp, ci, ci, ci, vp, ci, vp]),
         "ce_gpu_model_set_gemm": (ci, [vp, ci]),
         "ce_gpu_model_get_gemm": (ci, [vp, pi]),
+        "ce_gpu_gemm_mode_from_name": (ci, [ctypes.c_char_p, pi]),
         "ce_gpu_ctx_overflow": (ci, [vp, pi]),
         "ce_gpu_ctx_set_latency": (ci, [vp, ci]),
         "ce_gpu_ctx_set_fbank": (ci, [vp, ci]),
@@ -301,8 +303,10 @@ class Model:
     def set_gemm(self, mode):
         """Matrix-core form of the fp32 Linear layers: "fp32" (fp32 MFMA),
         "bf16x6" (three-plane bf16 split on the way into LDS, six products),
-        "bf16x6p" (the same with the planes stored in HBM; bit-identical) or
-        "f16x3" (two scaled fp16 planes, three products);
+        "bf16x6p" (the same with the planes stored in HBM; bit-identical),
+        "f16x3" (two scaled fp16 planes, three products) or "bf16" (both
+        operands rounded to bf16 once, one product, hidden activations kept
+        as bf16: not fp32-accurate, never a default);
         ce_gpu_model_set_gemm."""
         check(lib().ce_gpu_model_set_gemm(self.h, GEMM_MODES[mode]))
         return self
@@ -331,6 +335,15 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+def gemm_mode_from_name(name):
+    """The ce_gpu_model_set_gemm number of a mode name
+    (ce_gpu_gemm_mode_from_name; needs no device).  `name`: bytes, str or
+    None (NULL)."""
+    v = ctypes.c_int(-1)
+    check(lib().ce_gpu_gemm_mode_from_name(name.encode() if isinstance(name, str) else name, ctypes.byref(v)))
+    return v.value
 
 
 def quant_params_from_range(mn, mx):

@@ -95,6 +95,21 @@ Status AcousticModel::Read(const Configuration &conf) {
   if (rc != CE_GPU_OK) return Status::Corruption(util::Format("{}: {}", nnet_file, ce_gpu_last_error()));
   int pdfs = 0;
   ce_gpu_model_info(model_, nullptr, nullptr, &feat_dim_, &pdfs, nullptr, nullptr);
+  // gpu_gemm = <name>: the model's GEMM mode (ce_gpu_gemm_mode_from_name's
+  // names; "bf16" is the plain bf16 mode).  Beside gpu_int8_ranges it is
+  // accepted and has no effect: the int8 form wins.
+  const std::string gemm_name = conf.GetStringOrElse("gpu_gemm", "");
+  if (!gemm_name.empty()) {
+    int mode = 0;
+    int rcg = ce_gpu_gemm_mode_from_name(gemm_name.c_str(), &mode);
+    if (rcg == CE_GPU_OK) rcg = ce_gpu_model_set_gemm(model_, mode);
+    if (rcg != CE_GPU_OK) {
+      const std::string why = util::Format("gpu_gemm = {}: {}", gemm_name, ce_gpu_last_error());
+      ce_gpu_model_destroy(model_);
+      model_ = nullptr;
+      return rcg == CE_GPU_ENOTSUP ? Status::NotImplemented(why) : Status::Corruption(why);
+    }
+  }
   // gpu_int8_ranges = <path>: calibrated static int8.  The file is a VEC0 of
   // min0 max0 min1 max1 ... (one pair per Linear, e.g. what
   // ce_gpu_model_calibrate returned); its rows do not depend on the batch, so

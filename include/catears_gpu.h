@@ -68,7 +68,9 @@ const char *ce_gpu_last_error(void);
  * (ce_gpu_quant_params_from_range, ce_gpu_model_calibrate,
  * ce_gpu_model_quantize_static, ce_gpu_model_quant_params); the latency mode
  * of static int8 (ce_gpu_i8_latency_plan, ce_gpu_debug_i8_latency_launches,
- * the config key gpu_int8_ranges) only adds to 0.7. */
+ * the config key gpu_int8_ranges) only adds to 0.7, and so does the plain
+ * bf16 GEMM mode (CE_GPU_GEMM_BF16, ce_gpu_gemm_mode_from_name, the config
+ * key gpu_gemm). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -225,6 +227,11 @@ int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
  * ce_gpu_model_calibrate returned); the loaded model is then switched with
  * ce_gpu_model_quantize_static.  A wrong count or a bad range fails with
  * that call's CE_GPU_EINVAL text prefixed with the file name.
+ * Another: gpu_gemm = <name> (a name of ce_gpu_gemm_mode_from_name) switches
+ * the loaded model with ce_gpu_model_set_gemm; an unknown name fails with
+ * CE_GPU_EINVAL and the key and value in the text, a mode the model does not
+ * allow with CE_GPU_ENOTSUP.  Beside gpu_int8_ranges it is accepted and has
+ * no effect (the int8 form wins).
  * Fails with CE_GPU_ENOTSUP for a topology whose whole-utterance result
  * would differ from the reference's chunked one. */
 int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_model **out);
@@ -332,7 +339,7 @@ int ce_gpu_model_quant_params(const ce_gpu_model *m, float *h_scale, int32_t *h_
  * multiples of 4, every ReLU/BatchNorm fused into a Linear), else FP32.
  * F16X3 (22-23 significant bits per operand, not a full fp32 significand)
  * is opt-in.  Only the experiments library (make EXPERIMENTS=1) reads the
- * environment's CATEARS_NNET_GEMM (0-3, the numbers below) as the default;
+ * environment's CATEARS_NNET_GEMM (0-4, the numbers below) as the default;
  * the product library reads no environment.  Setting a mode the model does
  * not allow returns CE_GPU_ENOTSUP. */
 #define CE_GPU_GEMM_FP32 0
@@ -342,8 +349,36 @@ int ce_gpu_model_quant_params(const ce_gpu_model *m, float *h_scale, int32_t *h_
  * epilogue writes its output split; 6 B per element instead of 4).  The same
  * products in the same order as BF16X6: bit-identical results. */
 #define CE_GPU_GEMM_BF16X6_PLANES 3
+/* Plain bf16: not an fp32-accurate mode, and never a default.  Definition:
+ *   - every Linear computes y_j = sum_k bf16(a_k) * bf16(w_kj), bf16(.) the
+ *     round-to-nearest-even of the fp32 value; the products are exact and
+ *     accumulated in fp32 in ascending K, in one accumulator per output
+ *     (one v_mfma_f32_16x16x32_bf16 per 32 k);
+ *   - bias / ReLU / BatchNorm are applied in fp32 in the reference's rounding
+ *     order, as in the other modes;
+ *   - a hidden Linear's output is stored as bf16(y) -- the same function as
+ *     rounding at the consumer, since in a program this mode accepts the only
+ *     consumer is the next Linear; the last Linear writes fp32, and the
+ *     finalize (LogSoftmax, minus log prior) is unchanged;
+ *   - every row depends on its own input rows only: its bits do not depend
+ *     on the row count, the tile shape the host picks, its position in the
+ *     block or what shares the launch (every tile shape uses the one MFMA
+ *     shape and K order, and there is no split-K).
+ * Same precondition as the other plane modes (CE_GPU_ENOTSUP otherwise).
+ * ce_gpu_ctx_set_latency and ce_gpu_ctx_set_wide_tiles are ignored in this
+ * mode; ce_gpu_model_calibrate refuses it (CE_GPU_ENOTSUP);
+ * ce_gpu_model_quantize(_static) behave as before, the int8 form winning
+ * over the GEMM mode.  bf16 has fp32's exponent range: no overflow word.
+ * Across layers the result is not independent of the fp32 summation order:
+ * a last-place difference in a hidden y can move bf16(y) by 2^-9 relative
+ * (DESIGN.md §5). */
+#define CE_GPU_GEMM_BF16 4
 int ce_gpu_model_set_gemm(ce_gpu_model *m, int mode);
 int ce_gpu_model_get_gemm(const ce_gpu_model *m, int *mode);
+/* The CE_GPU_GEMM_* number of a mode name: "fp32", "bf16x6", "bf16x6p"
+ * (CE_GPU_GEMM_BF16X6_PLANES), "f16x3", "bf16".  Any other name, or a NULL
+ * argument: CE_GPU_EINVAL.  Needs no device. */
+int ce_gpu_gemm_mode_from_name(const char *name, int *mode);
 
 /* tid2pdf map (AcousticModel::TransitionPdfIdMap, src/am.h:38-40).  Copies
  * min(capacity, size) ints to h_out and returns the size via *size. */
