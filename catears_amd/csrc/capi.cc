@@ -955,15 +955,39 @@ static int tap_input(ce_gpu_ctx *ctx, CalibTap *tap, const GemmLayer &g, const f
                          tap->ranges + 2 * tap->linear++);
 }
 
+// An incremental session chunk (inc, internal.h) runs every Linear causally:
+// the layer's splice offsets less their largest one.  Without inc: as they are.
+static int causal_shift(const GemmLayer &g, const IncrChunk *inc) {
+  if (!inc) return 0;
+  int mx = g.off[0];
+  for (int i = 1; i < g.nseg; ++i) mx = std::max(mx, g.off[i]);
+  return mx;
+}
+
+static void layer_offsets(const GemmLayer &g, const IncrChunk *inc, int *off) {
+  const int shift = causal_shift(g, inc);
+  for (int i = 0; i < 8; ++i) off[i] = inc && i >= g.nseg ? 0 : g.off[i] - shift;
+}
+
+// ... and exchanges the slots' cached context rows on Linear `linear`'s input
+// (rows of row_bytes bytes, ld_bytes apart) before the launch that reads it
+// through those offsets.
+static int exchange_input(ce_gpu_ctx *ctx, const IncrChunk *inc, int linear, const void *buf, size_t row_bytes,
+                          size_t ld_bytes, int32_t *rowsum = nullptr) {
+  if (!inc || linear == 0) return CE_GPU_OK;
+  return launch_session_exchange(ctx->stream, *inc, linear, const_cast<void *>(buf), row_bytes, ld_bytes, rowsum);
+}
+
 // Runs the program's steps on `rows` packed rows starting at x (row_map: the
 // first layer's packed row -> source row, or NULL for identity).  Returns the
 // last activation via *y / *ldy.
 static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                         const int *row_map, const float **y, int *ldy, CalibTap *tap = nullptr) {
+                         const int *row_map, const float **y, int *ldy, CalibTap *tap = nullptr,
+                         const IncrChunk *inc = nullptr) {
   const size_t per = (size_t)rows * m->max_width;
   CE_TRY(ensure_workspace(ctx, 2 * per));
   float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
-  int cur = 0;
+  int cur = 0, linear = 0;
   bool first = true;
   for (const Step &st : m->steps) {
     if (st.is_gemm) {
@@ -978,7 +1002,8 @@ static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
       a.kpad = g.kpad;
       a.din = g.din;
       a.nseg = g.nseg;
-      for (int i = 0; i < 8; ++i) a.off[i] = g.off[i];
+      layer_offsets(g, inc, a.off);
+      CE_TRY(exchange_input(ctx, inc, linear++, x, (size_t)g.din * 4, (size_t)ldx * 4));
       a.w = g.wt.as<float>();
       a.ldw = g.kpad;
       a.bias = g.bias.as<float>();
@@ -997,7 +1022,7 @@ static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
           // the fast kernel on it -- cheaper than a per-element gather loader.
           CE_TRY(ensure_scratch(ctx, (size_t)rows * g.kpad * sizeof(float)));
           float *xs = static_cast<float *>(ctx->scratch.ptr);
-          CE_TRY(launch_splice_pad(ctx->stream, x, ldx, rows, g.din, g.nseg, g.off, a.row_map, xs, g.kpad));
+          CE_TRY(launch_splice_pad(ctx->stream, x, ldx, rows, g.din, g.nseg, a.off, a.row_map, xs, g.kpad));
           a.x = xs;
           a.ldx = g.kpad;
           a.row_map = nullptr;
@@ -1067,7 +1092,8 @@ static bool lat_fused_final() {
 }
 
 static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                         const int *row_map, const float **y, int *ldy, LatTail *tail, CalibTap *tap = nullptr) {
+                         const int *row_map, const float **y, int *ldy, LatTail *tail, CalibTap *tap = nullptr,
+                         const IncrChunk *inc = nullptr) {
   int max_in = 0;
   for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
   for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
@@ -1099,16 +1125,18 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
     const bool lat_direct = i == 0 && g.din % 8 == 0 && ldx % 4 == 0 &&
                             (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                             (ctx->latency || (g.wdir.ptr && x6_first_direct()));
+    int off[8];
+    layer_offsets(g, inc, off);
     if (lat_direct) {
       xs = x;
       px = ldx;
       a.din = g.din;
       a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = g.off[s];
+      for (int s = 0; s < 8; ++s) a.off[s] = off[s];
       a.row_map = row_map;
     } else if (i == 0) {
       ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
-      CE_TRY(launch_splice_pad(ctx->stream, x, ldx, rows, g.din, g.nseg, g.off, row_map, buf[cur], g.kpad));
+      CE_TRY(launch_splice_pad(ctx->stream, x, ldx, rows, g.din, g.nseg, off, row_map, buf[cur], g.kpad));
       xs = buf[cur];
       px = g.kpad;
       cur ^= 1;
@@ -1117,7 +1145,9 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
     } else {
       a.din = g.din;
       a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = g.off[s];
+      for (int s = 0; s < 8; ++s) a.off[s] = off[s];
+      // (never the plane chain: an experiments-library knob, off by default)
+      CE_TRY(exchange_input(ctx, inc, (int)i, xs, (size_t)px * 4, (size_t)px * 4));
     }
     // planes into layer i / out of it: every layer after the first (mode 1),
     // or the output layer only (mode 2)
@@ -1253,7 +1283,7 @@ static int run_steps_x6(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, 
 // allocates nothing.  The context's latency and wide-tile settings are not
 // read: one kernel family, its tile a function of (rows, n).
 static int run_steps_bf16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                          const int *row_map, const float **y, int *ldy) {
+                          const int *row_map, const float **y, int *ldy, const IncrChunk *inc = nullptr) {
   int max_in = 0;
   for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
   for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
@@ -1269,9 +1299,11 @@ static int run_steps_bf16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x
     const GemmLayer &g = m->steps[i].gemm;
     const bool last = i + 1 == m->steps.size();
     X6Gemm a;
+    int off[8];
+    layer_offsets(g, inc, off);
     if (i == 0) {
       ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
-      CE_TRY(launch_splice_pad_bf16(ctx->stream, x, ldx, rows, g.din, g.nseg, g.off, row_map, sbuf[cur], g.kpad));
+      CE_TRY(launch_splice_pad_bf16(ctx->stream, x, ldx, rows, g.din, g.nseg, off, row_map, sbuf[cur], g.kpad));
       xs = sbuf[cur];
       px = g.kpad;
       cur ^= 1;
@@ -1280,7 +1312,8 @@ static int run_steps_bf16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x
     } else {
       a.din = g.din;
       a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = g.off[s];
+      for (int s = 0; s < 8; ++s) a.off[s] = off[s];
+      CE_TRY(exchange_input(ctx, inc, (int)i, xs, (size_t)px * 2, (size_t)px * 2));
     }
     a.x = xs;
     a.ldx = px;
@@ -1488,7 +1521,7 @@ static void i8_static_scratch(const ce_gpu_model *m, int rows, size_t *q_bytes, 
 // library, read per call: tools/i8_static.py) keeps the quantize pass
 // everywhere.
 static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                               const int *row_map, const float **y, int *ldy) {
+                               const int *row_map, const float **y, int *ldy, const IncrChunk *inc = nullptr) {
   const size_t per = (size_t)rows * m->max_width;
   CE_TRY(ensure_workspace(ctx, 2 * per));
   float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
@@ -1500,7 +1533,7 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
   int32_t *rs[3];
   for (int i = 0; i < 3; ++i) rs[i] = reinterpret_cast<int32_t *>(base + 2 * q_bytes + i * rs_bytes);
   const bool fused_ok = CE_KNOB("CATEARS_I8_FUSED", 1) != 0;
-  int cur = 0, qc = 0, rc = 0;
+  int cur = 0, qc = 0, rc = 0, linear = 0;
   bool first = true, have_bytes = false;  // have_bytes: the previous GEMM wrote xq[qc] / rs[rc]
   for (size_t si = 0; si < m->steps.size(); ++si) {
     const Step &st = m->steps[si];
@@ -1510,13 +1543,24 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
     }
     const I8Layer &L = st.i8;
     const int ldq = L.spliced ? L.kpad : L.in_width;
+    // an incremental chunk: the cached context joins the layer's input in the
+    // form it has here -- fp32 rows ahead of the quantize pass, or the bytes
+    // and row sums the previous GEMM wrote -- and whichever launch reads that
+    // input through the splice offsets reads it causally
+    int off[8];
+    layer_offsets(st.gemm, inc, off);
     if (!have_bytes) {
+      CE_TRY(exchange_input(ctx, inc, linear, x, (size_t)L.in_width * 4, (size_t)ldx * 4));
       ProfScope prof(ctx, CE_GPU_PROF_QUANT);
       const int zero[1] = {0};
       CE_TRY(launch_i8_quantize(ctx->stream, x, ldx, rows, L.in_width, first ? row_map : nullptr,
-                                L.spliced ? st.gemm.nseg : 1, L.spliced ? st.gemm.off : zero, L.qp, xq[qc], ldq, rs[rc],
+                                L.spliced ? st.gemm.nseg : 1, L.spliced ? off : zero, L.qp, xq[qc], ldq, rs[rc],
                                 rs[(rc + 1) % 3]));
+    } else {
+      CE_TRY(exchange_input(ctx, inc, linear, xq[qc], (size_t)L.in_width, (size_t)ldq, rs[rc]));
     }
+    ++linear;
+    const int shift = L.spliced ? 0 : causal_shift(st.gemm, inc);
     const I8Layer *N = si + 1 < m->steps.size() && m->steps[si + 1].is_gemm ? &m->steps[si + 1].i8 : nullptr;
     const bool fuse = fused_ok && N && N->in_width == L.n && !N->spliced && i8_gemm_can_requantize(L, ldq);
     // latency mode: the split-K pair where the slice rule gives it this layer
@@ -1534,18 +1578,20 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
       const I8NextBytes nb = {xq[qc ^ 1], rs[(rc + 1) % 3], rs[(rc + 2) % 3], N->qp};
       if (lat_slices > 0)
         CE_TRY(launch_i8_lat(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, &nb,
-                             ctx->lat_part.as<int32_t>(), lat_words));
+                             ctx->lat_part.as<int32_t>(), lat_words, shift));
       else
-        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, nullptr, nullptr, &nb));
+        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, nullptr, nullptr, &nb,
+                              shift));
       qc ^= 1;
       rc = (rc + 1) % 3;
       x = nullptr;
     } else {
       if (lat_slices > 0)
         CE_TRY(launch_i8_lat(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n, nullptr,
-                             ctx->lat_part.as<int32_t>(), lat_words));
+                             ctx->lat_part.as<int32_t>(), lat_words, shift));
       else
-        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n));
+        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n, nullptr, nullptr, nullptr,
+                              shift));
       x = buf[cur];
       cur ^= 1;
     }
@@ -1560,8 +1606,18 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
 
 static int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
                      const int *row_map, const uint32_t *row_edge, const float **y, int *ldy,
-                     LatTail *tail = nullptr, CalibTap *tap = nullptr) {
+                     LatTail *tail = nullptr, CalibTap *tap = nullptr, const IncrChunk *inc = nullptr) {
   if (tail) tail->active = false;
+  if (inc) {
+    // an incremental session chunk (sessions_create_ex admitted these forms only)
+    if (tap || (m->int8 && !m->int8_static)) return fail(CE_GPU_EINVAL, "incremental chunk: unsupported form");
+    if (m->int8) return run_steps_i8_static(ctx, m, x, ldx, rows, row_map, y, ldy, inc);
+    if (m->gemm == CE_GPU_GEMM_BF16) return run_steps_bf16(ctx, m, x, ldx, rows, row_map, y, ldy, inc);
+    if (m->gemm == CE_GPU_GEMM_BF16X6 && x6_f32in() && x6_plane_chain_env() == 0)
+      return run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail, nullptr, inc);
+    if (m->gemm == CE_GPU_GEMM_FP32) return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy, nullptr, inc);
+    return fail(CE_GPU_ENOTSUP, "incremental chunk: GEMM modes fp32, bf16x6 and bf16 only");
+  }
   if (tap) {
     // calibration reads fp32 activations between the layers
     if (m->int8) return fail(CE_GPU_EINVAL, "model_calibrate: the model is already quantized");
@@ -1661,12 +1717,12 @@ static int quantize_weights(ce_gpu_ctx *ctx, Step &st) {
 }
 
 int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats, int rows, const int *row_src,
-                      const uint32_t *row_edge, const int *row_dst, float *d_loglik) {
+                      const uint32_t *row_edge, const int *row_dst, float *d_loglik, const IncrChunk *inc) {
   const float *y = nullptr;
   int ldy = 0;
   LatTail tail;
   CE_TRY(run_steps(ctx, m, feats, m->input_dim, rows, row_src, row_edge, &y, &ldy,
-                   lat_tail_ok(d_loglik, m->log_prior.as<float>()) ? &tail : nullptr));
+                   lat_tail_ok(d_loglik, m->log_prior.as<float>()) ? &tail : nullptr, nullptr, inc));
   ProfScope prof(ctx, CE_GPU_PROF_FINALIZE);
   return finalize_output(ctx, y, ldy, 0, rows, m->num_pdfs, m->final_log_softmax, m->log_prior.as<float>(), row_dst,
                          d_loglik, tail);

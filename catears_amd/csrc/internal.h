@@ -627,7 +627,7 @@ struct I8NextBytes {
 bool i8_gemm_can_requantize(const I8Layer &L, int lda);
 int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
                    const void *pa, float *y, int ldy, const I8NextMinMax *mm = nullptr, int *nparts = nullptr,
-                   const I8NextBytes *nb = nullptr);
+                   const I8NextBytes *nb = nullptr, int off_shift = 0);
 // Latency mode of the static int8 GEMMs (kernels/nnet_i8_lat.hip): K split
 // into slices, every slice's int32 partial tile stored, then summed by a
 // reduce kernel that forms the outputs (fp32, or the next layer's bytes and
@@ -647,8 +647,11 @@ size_t i8_lat_part_words(int rows, int n, int slices);
 bool i8_lat_eligible(const I8Layer &L, int lda);
 int64_t i8_lat_launch_count();  // i8_lat_gemm_kernel launches of this process
 // part: i8_lat_part_words(m, L.n, slices) int32 words, 16-byte aligned
+// off_shift (both launchers): segment s reads row r + L.a_off[s] - off_shift
+// (an incremental session's causal offsets)
 int launch_i8_lat(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
-                  const void *pa, float *y, int ldy, const I8NextBytes *nb, int32_t *part, size_t part_words);
+                  const void *pa, float *y, int ldy, const I8NextBytes *nb, int32_t *part, size_t part_words,
+                  int off_shift = 0);
 int launch_i8_params_fold(hipStream_t s, const void *part, int nparts, void *params);
 size_t i8_gemm_parts(int m, int n);
 int i8_k_align();
@@ -661,8 +664,13 @@ int launch_gemm_u8_ws(hipStream_t s, int m, int n, int k, const uint8_t *a, cons
 // ce_gpu_am_forward runs per plan chunk): packed row r reads feature row
 // row_src[r] of feats (input_dim wide) and, when row_dst[r] >= 0, becomes row
 // row_dst[r] of d_loglik.
+// `inc` (an incremental session set's chunk, below): every Linear runs with
+// its splice offsets re-based to off[s] - max(off), and the slots' cached
+// context rows are exchanged on each later Linear's input before it is read.
+struct IncrChunk;
 int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats, int rows, const int *row_src,
-                      const uint32_t *row_edge, const int *row_dst, float *d_loglik);
+                      const uint32_t *row_edge, const int *row_dst, float *d_loglik,
+                      const IncrChunk *inc = nullptr);
 // Grows the context's nnet workspaces to what score_packed_rows needs for
 // `rows` packed rows in any GEMM mode and in latency mode, so that later
 // calls of up to that many rows allocate nothing.
@@ -694,5 +702,48 @@ int launch_session_carry(hipStream_t s, const SessionPush *d_push, int n, float 
 // normalised ring instead.
 int launch_session_cmvn(hipStream_t s, const SessionPush *d_push, int n, int total_frames, const float *gstats,
                         const float *tmp, float *raw, int raw_cap, float *norm, int norm_cap, float *carry);
+
+// ---- incremental sessions (CE_GPU_SESSIONS_INCREMENTAL) ----
+//
+// With the offsets re-based to off[s] - max(off) every Linear is causal:
+// output row j reads input rows j - c .. j (c = max(off) - min(off)).  A
+// slot's block in a chunk is `lead` rows followed by its k new rows, at the
+// same packed positions in every layer; before Linear i >= 2 reads its input
+// buffer, the last c rows of the block's lead rows are filled from the
+// slot's cache of that layer (zeros for a slot at position 0) and the block's
+// last c rows become the new cache.
+
+// One block of one chunk (device image, written by the host).
+struct SessionBlock {
+  int32_t slot;
+  int32_t row0;   // the block's first (lead) row in the chunk
+  int32_t k;      // new rows behind the `lead` lead rows
+  int32_t fresh;  // the slot is at position 0: zeros instead of its cache
+};
+
+// The cache of one Linear's input: slot s's c rows at cache + s * c *
+// row_cap bytes, row_bytes <= row_cap of a row in use (the representation
+// the model's form gives that input); their int32 row sums (static int8,
+// fused boundary) at sums + s * c.
+struct IncrLayer {
+  int c = 0;
+  size_t row_cap = 0;
+  char *cache = nullptr;
+  int32_t *sums = nullptr;
+};
+
+struct IncrChunk {
+  const SessionBlock *blocks = nullptr;  // device
+  int n_blocks = 0;
+  int lead = 0;                          // H
+  const IncrLayer *layers = nullptr;     // host, one per Linear of the model
+  int n_layers = 0;
+};
+
+// session_ctx_exchange_kernel for Linear `linear`'s input buffer: rows of
+// row_bytes bytes, ld_bytes apart, both multiples of 4; rowsum (may be NULL):
+// the buffer's int32 row sums, exchanged with the layer's `sums`.
+int launch_session_exchange(hipStream_t s, const IncrChunk &inc, int linear, void *buf, size_t row_bytes,
+                            size_t ld_bytes, int32_t *rowsum);
 
 }  // namespace catears

@@ -1333,7 +1333,8 @@ bool i8_gemm_can_requantize(const I8Layer &L, int lda) {
 }
 
 int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
-                   const void *pa, float *y, int ldy, const I8NextMinMax *mm, int *nparts, const I8NextBytes *nb) {
+                   const void *pa, float *y, int ldy, const I8NextMinMax *mm, int *nparts, const I8NextBytes *nb,
+                   int off_shift) {
   I8Args p = {};
   if (nb) {
     if (!i8_gemm_can_requantize(L, lda)) return fail(CE_GPU_EINVAL, "int8 GEMM: no requantize epilogue for this layer");
@@ -1353,7 +1354,7 @@ int launch_i8_gemm(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, in
   p.m = m;
   p.din = L.a_din;
   p.nseg = L.a_nseg;
-  for (int i = 0; i < 8; ++i) p.off[i] = L.a_off[i];
+  for (int i = 0; i < 8; ++i) p.off[i] = i < L.a_nseg ? L.a_off[i] - off_shift : 0;
   p.rowsum = rowsum;
   p.w = L.wq.as<int8_t>();
   p.colsum = L.colsum.as<int32_t>();

@@ -258,7 +258,8 @@ bool i8_lat_eligible(const I8Layer &L, int lda) {
 int64_t i8_lat_launch_count() { return g_lat_launches.load(std::memory_order_relaxed); }
 
 int launch_i8_lat(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int m, const int32_t *rowsum,
-                  const void *pa, float *y, int ldy, const I8NextBytes *nb, int32_t *part, size_t part_words) {
+                  const void *pa, float *y, int ldy, const I8NextBytes *nb, int32_t *part, size_t part_words,
+                  int off_shift) {
   if (m <= 0) return CE_GPU_OK;
   int slices = 0, per = 0;
   i8_lat_plan(L.kpad, L.n, m, &slices, &per);
@@ -277,7 +278,7 @@ int launch_i8_lat(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int
   g.m = m;
   g.din = L.a_din;
   g.nseg = L.a_nseg;
-  for (int i = 0; i < 8; ++i) g.off[i] = L.a_off[i];
+  for (int i = 0; i < 8; ++i) g.off[i] = i < L.a_nseg ? L.a_off[i] - off_shift : 0;
   g.w = L.wq.as<int8_t>();
   g.n = L.n;
   g.kpad = L.kpad;
@@ -305,7 +306,7 @@ int launch_i8_lat(hipStream_t s, const I8Layer &L, const int8_t *a, int lda, int
   r.k = L.k;
   r.rowsum = rowsum;
   r.nseg = L.a_nseg;
-  for (int i = 0; i < 8; ++i) r.off[i] = L.a_off[i];
+  for (int i = 0; i < 8; ++i) r.off[i] = i < L.a_nseg ? L.a_off[i] - off_shift : 0;
   r.colsum = L.colsum.as<int32_t>();
   r.pa = pa;
   r.w_scale = L.w_scale;

@@ -12,7 +12,10 @@
 //                          the slot's carry, the window's leaving frames read
 //                          from the slot's ring of raw features;
 //   session_copy_kernel    without CMVN: the fbank temporary into the
-//                          normalised ring.
+//                          normalised ring;
+//   session_ctx_exchange_kernel  incremental sets: a Linear's cached context
+//                          rows into the lead rows of every block of a
+//                          chunk, the blocks' last rows back as the new cache.
 // Every kernel takes the push list (SessionPush, internal.h) the host wrote
 // for this call; block index = position in that list.
 #include <hip/hip_runtime.h>
@@ -124,6 +127,48 @@ __global__ __launch_bounds__(64) void session_copy_kernel(const SessionPush *__r
   for (int i = blockIdx.x; i < p.frames; i += gridDim.x) y[(int64_t)((p.t0 + i) % norm_cap) * kMel] = x[(int64_t)i * kMel];
 }
 
+// One thread owns one column chunk (a V: 16 bytes, or 4 where an operand is
+// not 16-byte aligned) of one block (SessionBlock, internal.h) through all of
+// that block's rows, so nothing it reads is written by another thread: no
+// barrier, no LDS.  First the c lead rows in front of the block's new rows
+// from the slot's cache (zeros for a fresh slot), then the block's last c
+// rows into the cache -- with k < c some of those are lead rows the thread
+// has just written, which is why the order matters and why the buffer and the
+// cache are not __restrict__.  The row-sum words of a block (static int8) are
+// one such column, moved by one thread with plain stores: the GEMM that
+// added into them has finished.
+constexpr int kXchgThreads = 256;
+
+__device__ __forceinline__ uint4 xchg_zero(uint4 *) { return make_uint4(0u, 0u, 0u, 0u); }
+__device__ __forceinline__ uint32_t xchg_zero(uint32_t *) { return 0u; }
+
+template <typename V>
+__global__ __launch_bounds__(kXchgThreads) void session_ctx_exchange_kernel(const SessionBlock *__restrict__ blocks,
+                                                                            char *buf, int64_t ld_bytes, int ncol,
+                                                                            int lead, int c, char *cache,
+                                                                            int64_t row_cap, int32_t *rowsum,
+                                                                            int32_t *sums) {
+  const SessionBlock b = blocks[blockIdx.y];
+  const int col = blockIdx.x * kXchgThreads + threadIdx.x;
+  const int64_t first = b.row0 + lead - c;  // the first lead row this layer reads
+  if (col < ncol) {
+    char *x = buf + (int64_t)col * sizeof(V);
+    char *cp = cache + (int64_t)b.slot * c * row_cap + (int64_t)col * sizeof(V);
+    for (int j = 0; j < c; ++j) {
+      V v = xchg_zero(static_cast<V *>(nullptr));
+      if (!b.fresh) v = *reinterpret_cast<const V *>(cp + j * row_cap);
+      *reinterpret_cast<V *>(x + (first + j) * ld_bytes) = v;
+    }
+    for (int j = 0; j < c; ++j)
+      *reinterpret_cast<V *>(cp + j * row_cap) = *reinterpret_cast<const V *>(x + (first + b.k + j) * ld_bytes);
+  }
+  if (rowsum && blockIdx.x == 0 && threadIdx.x == 0) {
+    int32_t *sp = sums + (int64_t)b.slot * c;
+    for (int j = 0; j < c; ++j) rowsum[first + j] = b.fresh ? 0 : sp[j];
+    for (int j = 0; j < c; ++j) sp[j] = rowsum[first + b.k + j];
+  }
+}
+
 template <typename Sample>
 int launch_stage_t(hipStream_t s, const SessionPush *d_push, int n, int max_new, const Sample *pcm, float *stage,
                    int64_t stride) {
@@ -164,6 +209,31 @@ int launch_session_cmvn(hipStream_t s, const SessionPush *d_push, int n, int tot
     const int bx = std::min(total_frames, 256);
     hipLaunchKernelGGL(session_copy_kernel, dim3(bx, n), dim3(64), 0, s, d_push, tmp, norm, norm_cap);
   }
+  CE_HIP(hipGetLastError());
+  return CE_GPU_OK;
+}
+
+int launch_session_exchange(hipStream_t s, const IncrChunk &inc, int linear, void *buf, size_t row_bytes,
+                            size_t ld_bytes, int32_t *rowsum) {
+  if (linear < 0 || linear >= inc.n_layers) return fail(CE_GPU_EINVAL, "session exchange: no such layer");
+  const IncrLayer &l = inc.layers[linear];
+  if (l.c == 0 || inc.n_blocks == 0) return CE_GPU_OK;
+  if (!buf || !l.cache || l.c > inc.lead || row_bytes == 0 || row_bytes > l.row_cap || row_bytes > ld_bytes ||
+      (rowsum && !l.sums) || inc.n_blocks > 65535)
+    return fail(CE_GPU_EINVAL, "session exchange: bad geometry");
+  const uintptr_t mis = reinterpret_cast<uintptr_t>(buf) | reinterpret_cast<uintptr_t>(l.cache) | row_bytes |
+                        ld_bytes | l.row_cap;
+  if (mis & 3) return fail(CE_GPU_ENOTSUP, "session exchange: rows not 4-byte aligned");
+  const bool wide = (mis & 15) == 0;
+  const int ncol = (int)(row_bytes / (wide ? 16 : 4));
+  const dim3 grid((ncol + kXchgThreads - 1) / kXchgThreads, inc.n_blocks), block(kXchgThreads);
+  char *x = static_cast<char *>(buf);
+  if (wide)
+    hipLaunchKernelGGL(session_ctx_exchange_kernel<uint4>, grid, block, 0, s, inc.blocks, x, (int64_t)ld_bytes, ncol,
+                       inc.lead, l.c, l.cache, (int64_t)l.row_cap, rowsum, l.sums);
+  else
+    hipLaunchKernelGGL(session_ctx_exchange_kernel<uint32_t>, grid, block, 0, s, inc.blocks, x, (int64_t)ld_bytes,
+                       ncol, inc.lead, l.c, l.cache, (int64_t)l.row_cap, rowsum, l.sums);
   CE_HIP(hipGetLastError());
   return CE_GPU_OK;
 }

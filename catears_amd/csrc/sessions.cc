@@ -13,6 +13,16 @@
 // into one of kRing pinned buffers and copied with one hipMemcpyAsync; the
 // host waits for a ring entry only if its copy of kRing pushes ago is still
 // in flight.  Nothing is allocated, freed or synchronized on the way.
+//
+// An incremental set (CE_GPU_SESSIONS_INCREMENTAL) packs fewer rows.  With
+// every Linear's splice offsets re-based to off[s] - max(off) the nnet is a
+// chain of causal layers over the padded frame sequence (L copies of frame 0,
+// the frames, R copies of the last one at EOS): position p gives the output
+// row of time p - L - R.  A slot keeps, per Linear, the last c rows of that
+// layer's input (c = the span of its offsets), so a push that feeds it k
+// positions packs a block of H lead rows (H = the largest c) and k new rows
+// instead of k + L + R; session_ctx_exchange_kernel moves the cached rows in
+// and out per chunk and layer (score_packed_rows with an IncrChunk).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -50,7 +60,13 @@ struct RingEntry {
 struct Chunk {
   int rows = 0;
   int64_t map_base = 0;
+  int blk_base = 0, n_blocks = 0;  // incremental: its blocks in the push's block list
 };
+
+// The padded frames (positions) a slot has fed the nnet: nothing before its
+// first frame, then the L copies of frame 0 with it, the R copies of the last
+// frame with the EOS.
+int64_t positions(const Slot &s, int L, int R) { return s.frames == 0 ? 0 : L + s.frames + (s.eos ? R : 0); }
 
 }  // namespace
 
@@ -59,6 +75,13 @@ struct ce_gpu_sessions {
   const ce_gpu_model *m = nullptr;
   const float *gstats = nullptr;
   bool static_int8 = false;    // the model's form at create
+  int gemm = 0;                // ... its GEMM mode (checked by an incremental set only)
+  bool incremental = false;    // CE_GPU_SESSIONS_INCREMENTAL
+  int H = 0;                   // incremental: lead rows per block
+  int64_t max_blocks = 0;      // incremental: most blocks of one push
+  std::vector<IncrLayer> layers;  // incremental: one per Linear
+  DevBuf cache, cache_sums;       // ... their rows and row sums, all slots
+  int64_t n_pushes = 0, n_packed = 0, n_chunks = 0;  // ce_gpu_sessions_stats
   int n_slots = 0, max_chunk = 0, L = 0, R = 0;
   int max_frames = 0;          // most frames one push of one slot can complete
   int raw_cap = 0, norm_cap = 0;
@@ -90,6 +113,9 @@ int push_t(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_nu
   // the workspaces were sized for the form the model had at sessions_create
   if (m->int8_static != s->static_int8)
     return fail(CE_GPU_EINVAL, "sessions_push: the model was quantized after sessions_create");
+  // an incremental set's caches hold rows in the representation of that form
+  if (s->incremental && !m->int8_static && m->gemm != s->gemm)
+    return fail(CE_GPU_EINVAL, "sessions_push: the model's GEMM mode changed after sessions_create_ex");
   const int L = s->L, R = s->R;
 
   // 1. every count of the push, by arithmetic alone
@@ -169,9 +195,40 @@ int push_t(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_nu
   // chunk's remaining room starts a fresh chunk; a block larger than a chunk
   // is split into segments overlapping by L + R)
   int32_t *src = reinterpret_cast<int32_t *>(h + o_maps);
-  int64_t packed = 0;
+  int64_t packed = 0, n_blocks = 0;
   s->chunks.clear();
-  {
+  const int H = s->H;
+  // incremental: every block of the push in order -- f(push i, starts a new
+  // chunk, first row in its chunk, first position, positions).  A block that
+  // does not fit the chunk's remaining room starts a new chunk; one larger
+  // than a chunk is cut into blocks that each fill their chunk, so a chunk
+  // never holds two blocks of one slot (the second's lead rows come from the
+  // cache the first one leaves, and chunks run in stream order).
+  auto each_block = [&](auto &&f) {
+    int cur_rows = 0;
+    for (int i = 0; i < n; ++i) {
+      int64_t p = positions(s->slots[h_slot[i]], L, R);
+      const int64_t p1 = positions(s->next[i], L, R);
+      while (p < p1) {
+        int64_t room = kMaxRows - cur_rows - H;
+        const bool fresh_chunk = room < p1 - p && cur_rows > 0;
+        if (fresh_chunk) {
+          cur_rows = 0;
+          room = kMaxRows - H;
+        }
+        const int64_t k = std::min(p1 - p, room);
+        f(i, fresh_chunk, cur_rows, p, k);
+        cur_rows += (int)(H + k);
+        p += k;
+      }
+    }
+  };
+  if (s->incremental) {
+    each_block([&](int, bool, int, int64_t, int64_t k) {
+      packed += H + k;
+      ++n_blocks;
+    });
+  } else {
     // first pass over the geometry only: the three maps are laid out behind
     // one another, so their length must be known before they are written
     int cur_rows = 0;
@@ -193,9 +250,48 @@ int push_t(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_nu
   if (packed > s->max_packed) return fail(CE_GPU_EINVAL, "sessions_push: internal: map bound exceeded");
   int32_t *dst = src + packed;
   uint32_t *edge = reinterpret_cast<uint32_t *>(dst + packed);
-  const size_t used = o_maps + 12 * (size_t)packed;
-  if (used > s->desc_bytes) return fail(CE_GPU_EINVAL, "sessions_push: internal: descriptor bound exceeded");
-  {
+  const size_t o_blocks = align16(o_maps + 12 * (size_t)packed);
+  const size_t used = s->incremental ? o_blocks + sizeof(SessionBlock) * (size_t)n_blocks : o_maps + 12 * (size_t)packed;
+  if (used > s->desc_bytes || n_blocks > s->max_blocks)
+    return fail(CE_GPU_EINVAL, "sessions_push: internal: descriptor bound exceeded");
+  if (s->incremental) {
+    // block row j holds position p - H + j: the frame of that position from
+    // the ring (clamped to [0, last], which is the padding), an output row
+    // for the new rows at positions >= L + R
+    SessionBlock *blk = reinterpret_cast<SessionBlock *>(h + o_blocks);
+    Chunk cur;
+    int64_t at = 0, nb = 0, out_base = 0;
+    int out_of = 0;
+    each_block([&](int i, bool fresh_chunk, int row0, int64_t p, int64_t k) {
+      if (fresh_chunk) {
+        s->chunks.push_back(cur);
+        cur = Chunk();
+        cur.map_base = at;
+        cur.blk_base = (int)nb;
+      }
+      const Slot &was = s->slots[h_slot[i]], &nx = s->next[i];
+      for (; out_of < i; ++out_of) out_base += h_rows_out[out_of];  // the rows of the pushes before i
+      const int64_t ring_base = (int64_t)h_slot[i] * s->norm_cap, last = nx.frames - 1;
+      const int64_t seg_rows = H + k;
+      for (int64_t j = 0; j < seg_rows; ++j, ++at) {
+        const uint32_t dl = (uint32_t)std::min<int64_t>(j, 0xffff), dr = (uint32_t)std::min<int64_t>(seg_rows - 1 - j, 0xffff);
+        edge[at] = dl | (dr << 16);
+        const int64_t q = p - H + j;
+        int64_t fr = q - L;
+        fr = fr < 0 ? 0 : (fr > last ? last : fr);
+        src[at] = (int32_t)(ring_base + fr % s->norm_cap);
+        dst[at] = j >= H && q >= L + R ? (int32_t)(out_base + (q - L - R - was.rows)) : -1;
+      }
+      SessionBlock &b = blk[nb++];
+      b.slot = h_slot[i];
+      b.row0 = row0;
+      b.k = (int32_t)k;
+      b.fresh = p == 0;
+      cur.rows += (int)seg_rows;
+      ++cur.n_blocks;
+    });
+    if (cur.rows > 0) s->chunks.push_back(cur);
+  } else {
     Chunk cur;
     int64_t at = 0, out_base = 0;
     auto close = [&]() {
@@ -265,10 +361,69 @@ int push_t(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_nu
   const int *d_src = reinterpret_cast<const int *>(d + o_maps);
   const int *d_dst = d_src + packed;
   const uint32_t *d_edge = reinterpret_cast<const uint32_t *>(d_dst + packed);
-  for (const Chunk &c : s->chunks)
+  IncrChunk inc;
+  inc.lead = H;
+  inc.layers = s->layers.data();
+  inc.n_layers = (int)s->layers.size();
+  for (const Chunk &c : s->chunks) {
+    inc.blocks = reinterpret_cast<const SessionBlock *>(d + o_blocks) + c.blk_base;
+    inc.n_blocks = c.n_blocks;
     CE_TRY(score_packed_rows(ctx, m, s->norm.as<float>(), c.rows, d_src + c.map_base, d_edge + c.map_base,
-                             d_dst + c.map_base, d_loglik));
+                             d_dst + c.map_base, d_loglik, s->incremental ? &inc : nullptr));
+  }
   for (int i = 0; i < n; ++i) s->slots[h_slot[i]] = s->next[i];
+  ++s->n_pushes;
+  s->n_packed += packed;
+  s->n_chunks += (int64_t)s->chunks.size();
+  return CE_GPU_OK;
+}
+
+// The caches of an incremental set: per Linear after the first, c rows per
+// slot of the widest representation its input can have (fp32), and their row
+// sums; H = the largest c of any Linear.
+int create_caches(ce_gpu_sessions *s) {
+  const ce_gpu_model *m = s->m;
+  if (!m->int8_static && m->gemm != CE_GPU_GEMM_FP32 && m->gemm != CE_GPU_GEMM_BF16X6 && m->gemm != CE_GPU_GEMM_BF16)
+    return fail(CE_GPU_ENOTSUP, "sessions_create_ex: incremental sets take GEMM modes fp32, bf16x6 and bf16");
+  int sum_hi = 0, sum_lo = 0, prev_n = 0;
+  size_t bytes = 0, words = 0;
+  for (const Step &st : m->steps) {
+    if (!st.is_gemm) continue;
+    const GemmLayer &g = st.gemm;
+    int lo = g.off[0], hi = g.off[0];
+    for (int i = 1; i < g.nseg; ++i) lo = std::min(lo, g.off[i]), hi = std::max(hi, g.off[i]);
+    // the loaders carry a splice offset as a signed byte
+    if (lo - hi < -127) return fail(CE_GPU_ENOTSUP, "sessions_create_ex: a layer's splice span exceeds 127 rows");
+    sum_lo += lo, sum_hi += hi;
+    IncrLayer l;
+    l.c = hi - lo;
+    s->H = std::max(s->H, l.c);
+    if (!s->layers.empty() && l.c > 0) {
+      if (g.din != prev_n) return fail(CE_GPU_ENOTSUP, "sessions_create_ex: a layer's input is not the previous layer's output");
+      l.row_cap = (size_t)((g.din + 31) / 32 * 32) * sizeof(float);
+      bytes += (size_t)s->n_slots * l.c * l.row_cap;
+      words += (size_t)s->n_slots * l.c;
+    }
+    s->layers.push_back(l);
+    prev_n = g.n;
+  }
+  // position p = output time p - L - R only if the offsets add up to the context
+  if (-sum_lo != s->L || sum_hi != s->R)
+    return fail(CE_GPU_ENOTSUP, "sessions_create_ex: the layers' splice offsets do not add up to the model's context");
+  if (s->H >= kMaxRows) return fail(CE_GPU_EINVAL, "sessions_create_ex: nnet context too large");
+  if (bytes == 0) return CE_GPU_OK;
+  CE_TRY(s->cache.alloc(bytes));
+  CE_TRY(s->cache_sums.alloc(words * sizeof(int32_t)));
+  char *at = s->cache.as<char>();
+  int32_t *sums = s->cache_sums.as<int32_t>();
+  for (size_t i = 1; i < s->layers.size(); ++i) {
+    IncrLayer &l = s->layers[i];
+    if (l.c == 0) continue;
+    l.cache = at;
+    l.sums = sums;
+    at += (size_t)s->n_slots * l.c * l.row_cap;
+    sums += (size_t)s->n_slots * l.c;
+  }
   return CE_GPU_OK;
 }
 
@@ -278,10 +433,16 @@ extern "C" {
 
 int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *d_global_stats, int n_slots,
                            int max_chunk_samples, ce_gpu_sessions **out) {
+  return ce_gpu_sessions_create_ex(ctx, m, d_global_stats, n_slots, max_chunk_samples, 0, out);
+}
+
+int ce_gpu_sessions_create_ex(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *d_global_stats, int n_slots,
+                              int max_chunk_samples, unsigned flags, ce_gpu_sessions **out) {
   if (!out) return fail(CE_GPU_EINVAL, "out is NULL");
   *out = nullptr;
   if (!ctx || !m || n_slots < 1 || n_slots > 65535 || max_chunk_samples < 1)
     return fail(CE_GPU_EINVAL, "sessions_create: bad argument");
+  if (flags & ~CE_GPU_SESSIONS_INCREMENTAL) return fail(CE_GPU_EINVAL, "sessions_create_ex: unknown flag");
   // a static int8 model (frozen activation parameters) scores a row from its
   // own input rows alone, like the fp32 forms
   if (m->int8 && !m->int8_static)
@@ -298,6 +459,8 @@ int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *
   s->ctx = ctx;
   s->m = m;
   s->static_int8 = m->int8_static;
+  s->gemm = m->gemm;
+  s->incremental = (flags & CE_GPU_SESSIONS_INCREMENTAL) != 0;
   s->gstats = d_global_stats;
   s->n_slots = n_slots;
   s->max_chunk = max_chunk_samples;
@@ -313,13 +476,22 @@ int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *
   // a slot's push emits at most max_frames + R rows (EOS releases the R held back)
   const int64_t rows_max = max_frames + R, segs = rows_max / (kMaxRows - L - R) + 2;
   s->max_packed = (int64_t)n_slots * (rows_max + segs * (L + R));
+  if (s->incremental) {
+    CE_TRY(create_caches(s.get()));
+    // a slot's push feeds at most L + max_frames + R positions, every block
+    // of them behind H lead rows
+    const int64_t pos_max = L + max_frames + R, blocks = pos_max / (kMaxRows - s->H) + 2;
+    s->max_blocks = (int64_t)n_slots * blocks;
+    s->max_packed = (int64_t)n_slots * (pos_max + blocks * s->H);
+  }
   s->slots.assign(n_slots, Slot());
   s->next.assign(n_slots, Slot());
   s->seen.assign(n_slots, 0);
   s->chunks.reserve((size_t)(s->max_packed / (kMaxRows / 2) + n_slots + 2));
   const int fpb = fbank_frames_per_block();
   s->desc_bytes = align16(sizeof(SessionPush) * n_slots) + 2 * align16(8 * (size_t)(n_slots + 1)) +
-                  align16(4 * (size_t)((int64_t)n_slots * max_frames / fpb + 2)) + 12 * (size_t)s->max_packed + 64;
+                  align16(4 * (size_t)((int64_t)n_slots * max_frames / fpb + 2)) + 12 * (size_t)s->max_packed + 64 +
+                  sizeof(SessionBlock) * (size_t)s->max_blocks;
   const size_t f = sizeof(float);
   CE_TRY(s->stage.alloc((size_t)n_slots * s->stride * f));
   CE_TRY(s->tmp.alloc((size_t)n_slots * max_frames * kMel * f));
@@ -362,10 +534,21 @@ int ce_gpu_sessions_destroy(ce_gpu_sessions *s) {
   return CE_GPU_OK;
 }
 
+int ce_gpu_sessions_stats(const ce_gpu_sessions *s, int *lead_rows, int64_t *pushes, int64_t *packed_rows,
+                          int64_t *chunks) {
+  if (!s) return fail(CE_GPU_EINVAL, "sessions_stats: bad argument");
+  if (lead_rows) *lead_rows = s->incremental ? s->H : 0;
+  if (pushes) *pushes = s->n_pushes;
+  if (packed_rows) *packed_rows = s->n_packed;
+  if (chunks) *chunks = s->n_chunks;
+  return CE_GPU_OK;
+}
+
 int ce_gpu_sessions_reset(ce_gpu_sessions *s, int slot) {
   if (!s || slot < 0 || slot >= s->n_slots) return fail(CE_GPU_EINVAL, "sessions_reset: bad argument");
   // the device state needs no touch: a slot at frame 0 with an empty tail
-  // reads neither its carry nor its rings before it has rewritten them
+  // reads neither its carry nor its rings before it has rewritten them (nor,
+  // in an incremental set, its caches: at position 0 its blocks are fresh)
   s->slots[slot] = Slot();
   return CE_GPU_OK;
 }

@@ -39,6 +39,7 @@ ABI = [
     "ce_gpu_model_quant_params",
     "ce_gpu_i8_latency_plan", "ce_gpu_debug_i8_latency_launches",
     "ce_gpu_gemm_mode_from_name",
+    "ce_gpu_sessions_create_ex", "ce_gpu_sessions_stats",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -119,6 +120,8 @@ def lib():
         "ce_gpu_sum_f64_many": (ci, [vp, ci, ctypes.POINTER(vp), pi64, vp, vp]),
         "ce_gpu_debug_counters": (ci, [pi64, pi64]),
         "ce_gpu_sessions_create": (ci, [vp, vp, vp, ci, ci, pp]),
+        "ce_gpu_sessions_create_ex": (ci, [vp, vp, vp, ci, ci, ctypes.c_uint, pp]),
+        "ce_gpu_sessions_stats": (ci, [vp, pi, pi64, pi64, pi64]),
         "ce_gpu_sessions_destroy": (ci, [vp]),
         "ce_gpu_sessions_reset": (ci, [vp, ci]),
         "ce_gpu_sessions_push": (ci, [vp, ci, pi32, pi32, pi32, vp, vp, i64, pi32]),
@@ -467,6 +470,7 @@ def score(ctx, model, plan, pcm, global_stats=None, ws=None, out=None):
 
 
 SESSION_EOS = 1  # CE_GPU_SESSION_EOS
+SESSIONS_INCREMENTAL = 1  # CE_GPU_SESSIONS_INCREMENTAL
 
 
 def debug_counters():
@@ -498,17 +502,59 @@ class Sessions:
     """ce_gpu_sessions: `n_slots` live audio streams scored incrementally,
     their state (sample tail, CMVN sums and window, nnet context) on the
     device.  `global_stats`: the 41-float device tensor of ce_gpu_cmvn, or
-    None for no CMVN.  One per context."""
+    None for no CMVN.  One per context.
 
-    def __init__(self, ctx, model, n_slots, max_chunk_samples, global_stats=None):
+    `incremental` (CE_GPU_SESSIONS_INCREMENTAL): the set caches every layer's
+    context rows per slot, so a push packs k + H nnet rows per slot instead
+    of k + L + R (`packed_rows`); the same rows, counts and order."""
+
+    MAX_CHUNK_ROWS = 4096  # packed rows per launch sequence
+
+    def __init__(self, ctx, model, n_slots, max_chunk_samples, global_stats=None, incremental=False):
         self.ctx, self.model = ctx, model
         self.n_slots, self.max_chunk_samples = int(n_slots), int(max_chunk_samples)
         self._gstats = global_stats  # the library keeps the pointer
         self._state = [(0, 0, False)] * self.n_slots  # (samples, rows emitted, ended) per slot
+        self.incremental = bool(incremental)
         h = ctypes.c_void_p()
-        check(lib().ce_gpu_sessions_create(ctx.h, model.h, _ptr(global_stats), self.n_slots,
-                                           self.max_chunk_samples, ctypes.byref(h)))
+        if incremental:
+            check(lib().ce_gpu_sessions_create_ex(ctx.h, model.h, _ptr(global_stats), self.n_slots,
+                                                  self.max_chunk_samples, SESSIONS_INCREMENTAL, ctypes.byref(h)))
+        else:
+            check(lib().ce_gpu_sessions_create(ctx.h, model.h, _ptr(global_stats), self.n_slots,
+                                               self.max_chunk_samples, ctypes.byref(h)))
         self.h = h
+
+    def stats(self):
+        """ce_gpu_sessions_stats: host counters since create, as a dict --
+        lead_rows (H; 0 when not incremental), pushes, packed_rows, chunks."""
+        lead, pushes, packed, chunks = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        check(lib().ce_gpu_sessions_stats(self.h, ctypes.byref(lead), ctypes.byref(pushes), ctypes.byref(packed),
+                                          ctypes.byref(chunks)))
+        return {"lead_rows": lead.value, "pushes": pushes.value, "packed_rows": packed.value, "chunks": chunks.value}
+
+    @staticmethod
+    def packed_rows(L, R, H, sample_counts, eos_at, incremental):
+        """The packed nnet rows each push of one slot costs (the schedule()
+        arguments; a push's total is the sum over its slots).  Not
+        incremental: a push that emits r rows packs them with L + R context
+        rows, once per piece when they do not fit one chunk of 4096 rows.
+        Incremental: a push feeds positions -- L copies of frame 0 with the
+        slot's first frame, its new frames, R copies of the last frame at
+        the end -- behind H lead rows per piece.  Pure arithmetic."""
+        frames_out, rows_out = Sessions.schedule(L, R, sample_counts, eos_at)
+        ctx = H if incremental else L + R
+        room = Sessions.MAX_CHUNK_ROWS - ctx
+        out, frames = [], 0
+        for i, (f, r) in enumerate(zip(frames_out, rows_out)):
+            if incremental:
+                eos = eos_at is not None and i == eos_at
+                k = f + (L if frames == 0 and f > 0 else 0) + (R if eos and frames + f > 0 else 0)
+            else:
+                k = r
+            frames += f
+            out.append(k + -(-k // room) * ctx)
+        return out
 
     @staticmethod
     def _advance(right, samples, rows, count, eos):

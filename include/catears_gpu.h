@@ -70,7 +70,8 @@ const char *ce_gpu_last_error(void);
  * of static int8 (ce_gpu_i8_latency_plan, ce_gpu_debug_i8_latency_launches,
  * the config key gpu_int8_ranges) only adds to 0.7, and so does the plain
  * bf16 GEMM mode (CE_GPU_GEMM_BF16, ce_gpu_gemm_mode_from_name, the config
- * key gpu_gemm). */
+ * key gpu_gemm), and so do the incremental session sets
+ * (ce_gpu_sessions_create_ex, ce_gpu_sessions_stats). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -521,6 +522,27 @@ int ce_gpu_score_s16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan *
  * max_chunk_samples: the most samples one slot may receive in one push. */
 int ce_gpu_sessions_create(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *d_global_stats,
                            int n_slots, int max_chunk_samples, ce_gpu_sessions **out);
+/* The same with flags (0: exactly ce_gpu_sessions_create; an unknown bit:
+ * CE_GPU_EINVAL).
+ *
+ * CE_GPU_SESSIONS_INCREMENTAL: the set keeps, per slot and per Linear, the
+ * last c rows of that layer's input (c = the span of the layer's splice
+ * indices), so a push of k new positions packs k + H nnet rows per slot (H =
+ * the largest c) instead of k + L + R.  The contract of push / push_s16 /
+ * reset is unchanged: the same row counts, the same order, the same bits.
+ * GEMM modes fp32, bf16x6 and bf16 and static int8, with latency mode on or
+ * off; CE_GPU_GEMM_BF16X6_PLANES and CE_GPU_GEMM_F16X3: CE_GPU_ENOTSUP.  The
+ * set records the model's form (GEMM mode, static int8) at create; a push
+ * after it changed is CE_GPU_EINVAL and changes no state. */
+#define CE_GPU_SESSIONS_INCREMENTAL 1u
+int ce_gpu_sessions_create_ex(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *d_global_stats,
+                              int n_slots, int max_chunk_samples, unsigned flags, ce_gpu_sessions **out);
+/* Host counters since create (no device access; any pointer may be NULL):
+ * lead_rows = H (0 when the set is not incremental), the pushes that
+ * succeeded (n > 0), the packed nnet rows they scored and the chunks (launch
+ * sequences of at most 4096 packed rows) those ran as. */
+int ce_gpu_sessions_stats(const ce_gpu_sessions *s, int *lead_rows, int64_t *pushes, int64_t *packed_rows,
+                          int64_t *chunks);
 /* Waits for the pushes in flight, then frees the set.  Destroy it before its
  * context and its model. */
 int ce_gpu_sessions_destroy(ce_gpu_sessions *s);

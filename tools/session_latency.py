@@ -18,7 +18,10 @@ Both legs compute the same rows (checked once per N, bit for bit).
   python tools/session_latency.py --static-int8 [ticks] [rounds]
       the 64-stream push only: the bf16x6 latency-mode model beside a static
       int8 model (ce_gpu_model_quantize_static) on a throughput context and
-      on a latency-mode context, see static_int8()"""
+      on a latency-mode context, see static_int8()
+  python tools/session_latency.py --incremental [--slots N] [--tick-ms T] [ticks] [rounds]
+      an incremental set (CE_GPU_SESSIONS_INCREMENTAL) beside a plain one,
+      in three forms of the model, see incremental()"""
 import json
 import os
 import sys
@@ -193,9 +196,88 @@ def static_int8(ticks=100, rounds=3, n=64):
         sess.close()
 
 
+def incremental(ticks=100, rounds=3, n=64, tick_ms=100):
+    """N running streams, tick_ms of audio per slot and push, no CMVN: an
+    incremental set and a plain (flags = 0) set of the same model on two
+    contexts, in alternating blocks of `ticks` pushes, for static int8 and
+    bf16x6 (both on latency-mode contexts) and plain bf16.  The tick's PCM is
+    already on the device (the same buffer every tick: 13 MB a tick at 2048
+    slots would otherwise be most of what is timed); a host clock brackets
+    push + synchronise.  Packed rows per push from ce_gpu_sessions_stats; the
+    last tick's rows of the two sets are compared bit for bit."""
+    mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
+    conf = synth.write_model(mdir, "tdnn-s")
+    chunk = 16 * tick_ms
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "model": "tdnn-s", "slots": n, "tick_ms": tick_ms,
+                      "ticks": ticks, "rounds": rounds, "legs": ["incremental", "plain"],
+                      "version": gpu.lib().ce_gpu_version().decode()}), flush=True)
+    cal = [synth.pcm(2900 + i, 48000) for i in range(4)]
+    base = np.stack([synth.pcm(3000 + s, 4000 + chunk) for s in range(8)])
+    lead = torch.from_numpy(np.concatenate([np.roll(base[s % 8], 5 * s)[:4000] for s in range(n)])).cuda()
+    tick = torch.from_numpy(np.concatenate([np.roll(base[s % 8], 5 * s)[4000:] for s in range(n)])).cuda()
+    slots = list(range(n))
+    for form in ("static_int8_latency", "bf16", "bf16x6_latency"):
+        legs = []
+        for inc in (True, False):
+            ctx = gpu.Context(0)
+            model = gpu.Model(ctx, conf)
+            if form != "bf16":
+                ctx.set_latency(True)
+            if form == "bf16":
+                model.set_gemm("bf16")
+            if form == "static_int8_latency":
+                plan = gpu.Plan(ctx, [len(w) for w in cal], model)
+                model.quantize_static(ctx, model.calibrate(
+                    ctx, plan, gpu.fbank(ctx, plan, torch.from_numpy(np.concatenate(cal)).cuda())))
+                plan.close()
+            sess = gpu.Sessions(ctx, model, n, 4000, incremental=inc)
+            sess.push(slots, lead, [4000] * n)  # every slot running: 23 frames, 13 rows out
+            legs.append((ctx, model, sess))
+        out = torch.empty((n * (chunk // 160 + 1), legs[0][1].num_pdfs), dtype=torch.float32, device="cuda")
+        times, packed, last = ([], []), [0, 0], [None, None]
+        counters = None
+        for r in range(rounds + 1):
+            for k, (ctx, _, sess) in enumerate(legs):
+                before = sess.stats()
+                for _ in range(ticks):
+                    t0 = time.perf_counter()
+                    o, _rows = sess.push(slots, tick, [chunk] * n, out=out)
+                    ctx.synchronize()
+                    if r:  # block 0 is the warm-up
+                        times[k].append(time.perf_counter() - t0)
+                after = sess.stats()
+                packed[k] = (after["packed_rows"] - before["packed_rows"]) // ticks
+                chunks = (after["chunks"] - before["chunks"]) // ticks
+                last[k] = (o.cpu().numpy().copy(), chunks)
+            if r == 0:
+                counters = gpu.debug_counters()
+        rec = {"form": form, "slots": n, "tick_ms": tick_ms, "timed_pushes": len(times[0]),
+               "lead_rows": legs[0][2].stats()["lead_rows"],
+               "pushes_allocated_nothing": gpu.debug_counters() == counters,
+               "rows_identical": bool(np.array_equal(last[0][0].view(np.uint32), last[1][0].view(np.uint32)))}
+        for k, name in enumerate(("incremental", "plain")):
+            v = times[k]
+            rec[name] = {"packed_rows_per_push": packed[k], "chunks_per_push": last[k][1],
+                         "median_us": round(pct(v, 50) * 1e6, 1), "p10_us": round(pct(v, 10) * 1e6, 1),
+                         "p90_us": round(pct(v, 90) * 1e6, 1)}
+        rec["plain_over_incremental"] = round(pct(times[1], 50) / pct(times[0], 50), 3)
+        print(json.dumps(rec), flush=True)
+        for _, _, sess in legs:
+            sess.close()
+
+
+def flag(name, default):
+    argv = sys.argv[1:]
+    return int(argv[argv.index(name) + 1]) if name in argv else default
+
+
 if __name__ == "__main__":
-    nums = [int(v) for v in sys.argv[1:] if not v.startswith("--")][:2]
-    if "--static-int8" in sys.argv[1:]:
+    argv = sys.argv[1:]
+    valued = {i + 1 for i, v in enumerate(argv) if v in ("--slots", "--tick-ms")}
+    nums = [int(v) for i, v in enumerate(argv) if not v.startswith("--") and i not in valued][:2]
+    if "--incremental" in argv:
+        incremental(*(nums + [100, 3][len(nums):]), n=flag("--slots", 64), tick_ms=flag("--tick-ms", 100))
+    elif "--static-int8" in sys.argv[1:]:
         static_int8(*nums)
     else:
         main(*nums)
