@@ -1,6 +1,7 @@
 // capi.cc -- extern "C" entry points of libcatears_hip (include/catears_gpu.h):
 // errors, contexts, model loading (NN02 / MAT0 / VEC0 / key=value config),
-// batch planning, and the host-side sequencing of the kernels.
+// batch planning, and the argument checking around the nnet programs
+// (nnet_programs.cc).
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -20,6 +21,7 @@
 
 #include "internal.h"
 #include "model_io.h"
+#include "nnet_programs.h"
 
 namespace catears {
 
@@ -103,8 +105,9 @@ static int upload_split(const std::vector<float> &wt, int n, int kpad, DevBuf *o
   return out->upload(sp.data(), sp.size() * 2);
 }
 
-// The direct-weight kernel's image (X6Gemm::wd): the same three planes in
-// MFMA A-fragment order, units zero-padded to a multiple of kX6DirUnits.
+// The direct-weight kernel's image (the bf16x6 launch's `wd`): the same three
+// planes in MFMA A-fragment order, units zero-padded to a multiple of
+// kX6DirUnits.
 static int upload_wdir(const std::vector<float> &wt, int n, int kpad, DevBuf *out) {
   const int npad = (n + kX6DirUnits - 1) / kX6DirUnits * kX6DirUnits, kt = kpad / 32;
   std::vector<uint16_t> img((size_t)npad * 3 * kpad, 0);
@@ -354,6 +357,63 @@ static int build_program(const std::vector<RawLayer> &layers, int left, int righ
   return CE_GPU_OK;
 }
 
+// Quantize (src/matrix.cc:329-387) of one weight matrix on the host at load
+// time: per-tensor parameters over the in x out MAT0 matrix, then the bytes
+// stored shifted (q - 128) and transposed (n x kpad, zero padded) for the
+// GEMM, with their column sums.
+static int quantize_weights(ce_gpu_ctx *ctx, Step &st) {
+  GemmLayer &g = st.gemm;
+  I8Layer &L = st.i8;
+  std::vector<float> wt((size_t)g.n * g.kpad);
+  CE_HIP(hipMemcpy(wt.data(), g.wt.ptr, wt.size() * 4, hipMemcpyDeviceToHost));
+  float mn = FLT_MAX, mx = FLT_MIN;  // FindMinMax (matrix.cc:329-345)
+  for (int j = 0; j < g.n; ++j)
+    for (int k = 0; k < g.k; ++k) {
+      const float v = wt[(size_t)j * g.kpad + k];
+      if (v > mx) mx = v;
+      if (v < mn) mn = v;
+    }
+  const double scale = (mx - mn) / 255.0;  // ComputeQuantizationParams (matrix.cc:348-362)
+  L.w_zp = (int32_t)round(-mn / scale);
+  L.w_scale = (float)scale;
+  const int ka = i8_k_align();
+  L.n = g.n;
+  L.k = g.k;
+  L.kpad = (g.k + ka - 1) / ka * ka;
+  std::vector<int8_t> q((size_t)g.n * L.kpad, 0);
+  std::vector<int32_t> colsum(g.n, 0);
+  for (int j = 0; j < g.n; ++j)
+    for (int k = 0; k < g.k; ++k) {
+      float v = wt[(size_t)j * g.kpad + k] / L.w_scale + L.w_zp;  // matrix.cc:378-386
+      v = std::max(0.0f, std::min(v, 255.0f));
+      const int b = (int)(uint8_t)roundf(v) - 128;
+      q[(size_t)j * L.kpad + k] = (int8_t)b;
+      colsum[j] += b;
+    }
+  CE_TRY(L.wq.upload(q.data(), q.size()));
+  CE_TRY(L.colsum.upload(colsum.data(), colsum.size() * 4));
+  L.in_width = g.din;
+  L.in_left = g.in_left;
+  L.in_right = g.in_right;
+  L.spliced = g.din % ka != 0;
+  if (L.spliced) {
+    L.a_din = L.kpad;
+    L.a_nseg = 1;
+    for (int i = 0; i < 8; ++i) L.a_off[i] = 0;
+  } else {
+    L.a_din = g.din;
+    L.a_nseg = g.nseg;
+    for (int i = 0; i < 8; ++i) L.a_off[i] = g.off[i];
+  }
+  L.bias = g.bias.as<float>();
+  L.bn_scale = g.bn_scale.as<float>();
+  L.bn_offset = g.bn_offset.as<float>();
+  for (int i = 0; i < 4; ++i) L.post[i] = g.post[i];
+  L.npost = g.npost;
+  (void)ctx;
+  return CE_GPU_OK;
+}
+
 // Nnet::Read into a device program; `rd` is positioned at the NN02 tag.
 // left/right < 0: take the context from the network's Narrow layers.
 static int read_program(ce_gpu_ctx *ctx, Reader &rd, int left, int right, ce_gpu_model *m) {
@@ -400,35 +460,7 @@ static int load_model(ce_gpu_ctx *ctx, const std::string &nnet, const std::strin
   return CE_GPU_OK;
 }
 
-// ------------------------------------------------------------ workspace --
-
-static int ensure_workspace(ce_gpu_ctx *ctx, size_t floats) {
-  if (ctx->workspace_floats >= floats) return CE_GPU_OK;
-  CE_HIP(hipStreamSynchronize(ctx->stream));  // old buffer may still be in use
-  CE_TRY(ctx->workspace.alloc(floats * sizeof(float)));
-  ctx->workspace_floats = floats;
-  return CE_GPU_OK;
-}
-
-static int ensure_scratch(ce_gpu_ctx *ctx, size_t bytes) {
-  if (ctx->scratch.bytes >= bytes) return CE_GPU_OK;
-  CE_HIP(hipStreamSynchronize(ctx->stream));
-  return ctx->scratch.alloc(bytes);
-}
-
-// the latency GEMM's slice partials (one window of rows)
-static int ensure_lat_part(ce_gpu_ctx *ctx, size_t floats) {
-#ifdef CATEARS_EXPERIMENTS
-  // the split-K fix-up's tickets (CATEARS_LAT_FIXUP, measured slower:
-  // DESIGN.md §8 round 6), zeroed once: every fix-up launch leaves them zero
-  if (!ctx->lat_tickets.ptr) {
-    CE_TRY(ctx->lat_tickets.upload(std::vector<unsigned>(kX6LatTickets, 0u).data(), kX6LatTickets * sizeof(unsigned)));
-  }
-#endif
-  if (ctx->lat_part.bytes >= floats * sizeof(float)) return CE_GPU_OK;
-  CE_HIP(hipStreamSynchronize(ctx->stream));
-  return ctx->lat_part.alloc(floats * sizeof(float));
-}
+// ------------------------------------------------------------ profiling --
 
 static hipEvent_t pool_event(ce_gpu_ctx *ctx) {
   if (!ctx->event_pool.empty()) {
@@ -881,20 +913,6 @@ int ce_gpu_plan_destroy(ce_gpu_plan *p) {
   return CE_GPU_OK;
 }
 
-}  // extern "C"
-
-// CATEARS_SKIP (measurement builds only, -DCATEARS_DIAG: wrong results, timing
-// only): launches left out of every call, to price each stage of a pipeline
-// by its absence -- 1 first GEMM layer, 2 finalize, 4 fbank, 8 CMVN, 16 last
-// GEMM layer, 32 the hidden GEMM layers, 64 the int8 path's min / max and
-// Quantize passes.  0 in the product library.
-static int diag_skip() {
-  static const int v = CE_KNOB("CATEARS_SKIP", 0);
-  return v;
-}
-
-extern "C" {
-
 int ce_gpu_fbank(ce_gpu_ctx *ctx, const ce_gpu_plan *p, const float *d_pcm, float *d_feats, float *d_mel) {
   if (!ctx || !p || (p->total_frames > 0 && (!d_pcm || !d_feats))) return fail(CE_GPU_EINVAL, "NULL argument");
   ProfScope prof(ctx, CE_GPU_PROF_FBANK);
@@ -929,863 +947,6 @@ int ce_gpu_cmvn(ce_gpu_ctx *ctx, const ce_gpu_plan *p, const float *d_global_sta
   return launch_cmvn(ctx->stream, p, d_global_stats, d_feats, d_out);
 }
 
-}  // extern "C"
-
-namespace catears {
-// CATEARS_SPLICE_FIRST=0 (experiments library) keeps the gather loader for
-// narrow segments (A/B).
-static bool splice_first_layer() {
-  static const bool on = CE_KNOB("CATEARS_SPLICE_FIRST", 1) != 0;
-  return on;
-}
-
-// ce_gpu_model_calibrate's tap: before each Linear runs, the (min, max) of
-// its input block (held rows only) is folded into ranges[2 * linear ..].
-struct CalibTap {
-  float *ranges = nullptr;  // device, 2 per Linear
-  void *part = nullptr;     // minmax partials (i8_params_scratch_bytes)
-  const uint32_t *row_edge = nullptr;
-  int linear = 0;
-};
-
-static int tap_input(ce_gpu_ctx *ctx, CalibTap *tap, const GemmLayer &g, const float *x, int ldx, int rows,
-                     const int *row_map) {
-  if (!tap) return CE_GPU_OK;
-  return launch_i8_range(ctx->stream, x, ldx, rows, g.din, row_map, tap->row_edge, g.in_left, g.in_right, tap->part,
-                         tap->ranges + 2 * tap->linear++);
-}
-
-// An incremental session chunk (inc, internal.h) runs every Linear causally:
-// the layer's splice offsets less their largest one.  Without inc: as they are.
-static int causal_shift(const GemmLayer &g, const IncrChunk *inc) {
-  if (!inc) return 0;
-  int mx = g.off[0];
-  for (int i = 1; i < g.nseg; ++i) mx = std::max(mx, g.off[i]);
-  return mx;
-}
-
-static void layer_offsets(const GemmLayer &g, const IncrChunk *inc, int *off) {
-  const int shift = causal_shift(g, inc);
-  for (int i = 0; i < 8; ++i) off[i] = inc && i >= g.nseg ? 0 : g.off[i] - shift;
-}
-
-// ... and exchanges the slots' cached context rows on Linear `linear`'s input
-// (rows of row_bytes bytes, ld_bytes apart) before the launch that reads it
-// through those offsets.
-static int exchange_input(ce_gpu_ctx *ctx, const IncrChunk *inc, int linear, const void *buf, size_t row_bytes,
-                          size_t ld_bytes, int32_t *rowsum = nullptr) {
-  if (!inc || linear == 0) return CE_GPU_OK;
-  return launch_session_exchange(ctx->stream, *inc, linear, const_cast<void *>(buf), row_bytes, ld_bytes, rowsum);
-}
-
-// Runs the program's steps on `rows` packed rows starting at x (row_map: the
-// first layer's packed row -> source row, or NULL for identity).  Returns the
-// last activation via *y / *ldy.
-static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                         const int *row_map, const float **y, int *ldy, CalibTap *tap = nullptr,
-                         const IncrChunk *inc = nullptr) {
-  const size_t per = (size_t)rows * m->max_width;
-  CE_TRY(ensure_workspace(ctx, 2 * per));
-  float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
-  int cur = 0, linear = 0;
-  bool first = true;
-  for (const Step &st : m->steps) {
-    if (st.is_gemm) {
-      const GemmLayer &g = st.gemm;
-      GemmArgs a;
-      a.x = x;
-      a.ldx = ldx;
-      a.row_map = first ? row_map : nullptr;
-      a.m = rows;
-      a.n = g.n;
-      a.k = g.k;
-      a.kpad = g.kpad;
-      a.din = g.din;
-      a.nseg = g.nseg;
-      layer_offsets(g, inc, a.off);
-      CE_TRY(exchange_input(ctx, inc, linear++, x, (size_t)g.din * 4, (size_t)ldx * 4));
-      a.w = g.wt.as<float>();
-      a.ldw = g.kpad;
-      a.bias = g.bias.as<float>();
-      a.bn_scale = g.bn_scale.as<float>();
-      a.bn_offset = g.bn_offset.as<float>();
-      for (int i = 0; i < 4; ++i) a.post[i] = g.post[i];
-      a.npost = g.npost;
-      a.y = buf[cur];
-      a.ldy = g.n;
-      CE_TRY(tap_input(ctx, tap, g, x, ldx, rows, a.row_map));
-      {
-        ProfScope prof(ctx, g.din % 32 == 0 ? CE_GPU_PROF_GEMM : CE_GPU_PROF_GEMM_GATHER);
-        if (g.din % 32 != 0 && splice_first_layer()) {
-          // Segments narrower than a K-tile (the 40-wide first layer):
-          // write the spliced block once (rows x kpad, zero padded) and run
-          // the fast kernel on it -- cheaper than a per-element gather loader.
-          CE_TRY(ensure_scratch(ctx, (size_t)rows * g.kpad * sizeof(float)));
-          float *xs = static_cast<float *>(ctx->scratch.ptr);
-          CE_TRY(launch_splice_pad(ctx->stream, x, ldx, rows, g.din, g.nseg, a.off, a.row_map, xs, g.kpad));
-          a.x = xs;
-          a.ldx = g.kpad;
-          a.row_map = nullptr;
-          a.k = g.kpad;  // the padding columns are zero on both sides
-          a.din = g.kpad;
-          a.nseg = 1;
-          for (int i = 0; i < 8; ++i) a.off[i] = 0;
-        }
-        CE_TRY(launch_gemm_f32(ctx->stream, a));
-      }
-      x = buf[cur];
-      ldx = g.n;
-      cur ^= 1;
-      first = false;
-    } else {
-      CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
-    }
-  }
-  *y = x;
-  *ldy = ldx;
-  return CE_GPU_OK;
-}
-// The bf16x6 program (kernels/gemm_bf16x6.hip): the first layer's spliced
-// block is written as three bf16 planes, every hidden layer's epilogue
-// writes its output split for the next, the last layer writes fp32.
-// bf16x6 with fp32 operands in HBM (gemm_bf16x6f_kernel: the split into
-// planes happens on the way into LDS): the layers chain fp32 activations as
-// the fp32 program does, the weights are the fp32 `wt` matrices.  4 B per
-// operand element through L2 instead of the planes' 6; measured +3 % over
-// the plane kernels (tools/ab.sh).
-// Default; CATEARS_X6_F32IN=0 selects the plane-operand kernels
-// (run_steps_x6: planes written by each epilogue, bit-identical results).
-static int x6_variant_env() {
-  static const int v = CE_KNOB("CATEARS_X6_VARIANT", 0);
-  return v;
-}
-
-static bool x6_f32in() {
-  static const bool v = CE_KNOB("CATEARS_X6_F32IN", 1) != 0;
-  return v;
-}
-
-// CATEARS_X6_FIRST=0 keeps the round-3 splice_pad launch before the first
-// layer's throughput GEMM (bit-identical; the default gathers in its loader)
-static bool x6_first_direct() {
-  static const bool v = CE_KNOB("CATEARS_X6_FIRST", 1) != 0;
-  return v && (x6_variant_env() == 0 || x6_variant_env() == 300);
-}
-
-// CATEARS_X6_CHAIN: the layers hand each other their outputs as bf16 planes
-// (the direct-weight kernel's OUT16 epilogue, read by its PIN loader), so
-// each activation is split once, in the epilogue that produces it, instead of
-// by every unit tile of the next layer that reads it.  Bit-identical to the
-// fp32 chain (tests/test_gpu_x6_variants.py).
-// 2: only the output layer reads planes (its 14 unit tiles would each split
-// the same activations), written by the layer before it.
-static int x6_plane_chain_env() {
-  static const int v = CE_KNOB("CATEARS_X6_CHAIN", 0);
-  return v;
-}
-
-// CATEARS_LAT_FUSED_FINAL=0 keeps the last layer's split-K reduce as its own
-// launch before the finalize (bit-identical; the default fuses the two)
-static bool lat_fused_final() {
-  static const bool v = CE_KNOB("CATEARS_LAT_FUSED_FINAL", 1) != 0;
-  return v;
-}
-
-static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                         const int *row_map, const float **y, int *ldy, LatTail *tail, CalibTap *tap = nullptr,
-                         const IncrChunk *inc = nullptr) {
-  int max_in = 0;
-  for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
-  for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
-  // the plane chain: the first layer gathers the caller's fp32 rows in its
-  // loader, every layer has the fragment image, the later layers' segments
-  // are whole K-tiles
-  const int chain_mode = x6_plane_chain_env();
-  bool planes = chain_mode != 0 && !ctx->latency && x6_first_direct() && m->steps[0].gemm.din % 8 == 0 &&
-               ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  for (size_t i = 0; planes && i < m->steps.size(); ++i)
-    planes = m->steps[i].gemm.wdir.ptr && (i == 0 || m->steps[i].gemm.din % 32 == 0);
-  // a block of planes is rows x 3 x width bf16: 1.5 floats per element
-  const size_t blk = ((size_t)rows * max_in * (planes ? 3 : 2) / 2 + 63) / 64 * 64;
-  CE_TRY(ensure_workspace(ctx, 2 * blk + (size_t)rows * m->num_pdfs));
-  float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + blk};
-  float *out = ctx->workspace.as<float>() + 2 * blk;
-  const float *xs = nullptr;
-  int px = 0, cur = 0;
-  ProfChain chain(ctx);  // every step below is one launch; GEMMs back to back
-  for (size_t i = 0; i < m->steps.size(); ++i) {
-    const GemmLayer &g = m->steps[i].gemm;
-    const bool last = i + 1 == m->steps.size();
-    X6Gemm a;
-    // calibration: the block entering this layer's Splice (the caller's rows,
-    // or the previous layer's fp32 output)
-    CE_TRY(i == 0 ? tap_input(ctx, tap, g, x, ldx, rows, row_map) : tap_input(ctx, tap, g, xs, px, rows, nullptr));
-    // the latency kernel and the default direct-weight kernel splice the
-    // caller's rows themselves (din % 8 == 0): no splice_pad launch
-    const bool lat_direct = i == 0 && g.din % 8 == 0 && ldx % 4 == 0 &&
-                            (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                            (ctx->latency || (g.wdir.ptr && x6_first_direct()));
-    int off[8];
-    layer_offsets(g, inc, off);
-    if (lat_direct) {
-      xs = x;
-      px = ldx;
-      a.din = g.din;
-      a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = off[s];
-      a.row_map = row_map;
-    } else if (i == 0) {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
-      CE_TRY(launch_splice_pad(ctx->stream, x, ldx, rows, g.din, g.nseg, off, row_map, buf[cur], g.kpad));
-      xs = buf[cur];
-      px = g.kpad;
-      cur ^= 1;
-      a.din = g.kpad;
-      a.nseg = 1;
-    } else {
-      a.din = g.din;
-      a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = off[s];
-      // (never the plane chain: an experiments-library knob, off by default)
-      CE_TRY(exchange_input(ctx, inc, (int)i, xs, (size_t)px * 4, (size_t)px * 4));
-    }
-    // planes into layer i / out of it: every layer after the first (mode 1),
-    // or the output layer only (mode 2)
-    const size_t nst = m->steps.size();
-    const bool pin = planes && i > 0 && (chain_mode != 2 || i + 1 == nst);
-    const bool pout = planes && !last && (chain_mode != 2 || i + 2 == nst);
-    if (pin) {
-      a.x = reinterpret_cast<const uint16_t *>(xs);
-      a.ldx = 3 * px;
-      a.px = px;
-    } else {
-      a.xf = xs;
-      a.ldx = px;
-    }
-    a.wf = g.wt.as<float>();
-    a.ldw = g.kpad;
-    a.w = g.wsplit.as<uint16_t>();  // the same weights as planes (kernels that read them)
-    a.pw = g.kpad;
-    a.wd = g.wdir.as<uint16_t>();   // and as MFMA fragments (the default kernel)
-    a.wd_kt = g.kpad / 32;
-    a.wide = ctx->wide_tiles != 0;
-    a.m = rows;
-    a.n = g.n;
-    a.kpad = i == 0 ? g.kpad : g.nseg * g.din;
-    a.bias = g.bias.as<float>();
-    a.bn_scale = g.bn_scale.as<float>();
-    a.bn_offset = g.bn_offset.as<float>();
-    for (int q = 0; q < 4; ++q) a.post[q] = g.post[q];
-    a.npost = g.npost;
-    const int pn = (g.n + 31) / 32 * 32;
-    if (pout) {
-      a.y16 = reinterpret_cast<uint16_t *>(buf[cur]);
-      a.ldy = 3 * pn;
-      a.py = pn;
-    } else {
-      a.y32 = last ? out : buf[cur];
-      a.ldy = last ? g.n : pn;
-    }
-    {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM);
-      if (ctx->latency) {
-        const size_t pf = x6_lat_part_floats(a.m, a.n, x6_lat_slices(a.kpad, a.n));
-        CE_TRY(ensure_lat_part(ctx, pf));
-        if (last && lat_fused_final()) a.tail = tail;  // the reduce may run inside the finalize
-        CE_TRY(launch_gemm_bf16x6_lat(ctx->stream, a, ctx->lat_part.as<float>(), pf, ctx->lat_tickets.as<unsigned>()));
-      } else if (!(diag_skip() & (i == 0 ? 1 : last ? 16 : 32))) {
-        CE_TRY(launch_gemm_bf16x6(ctx->stream, a));
-      }
-    }
-    xs = buf[cur];
-    px = pn;
-    cur ^= 1;
-  }
-  *y = out;
-  *ldy = m->steps.back().gemm.n;
-  return CE_GPU_OK;
-}
-
-static int run_steps_x6(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                        const int *row_map, const float **y, int *ldy) {
-  int max_in = 0;
-  for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
-  for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
-  // two split ping-pong blocks (rows x 3 x max_in bf16) + the fp32 output
-  const size_t split_floats = ((size_t)rows * 3 * max_in + 1) / 2;
-  const size_t split_stride = (split_floats + 63) / 64 * 64;
-  CE_TRY(ensure_workspace(ctx, 2 * split_stride + (size_t)rows * m->num_pdfs));
-  uint16_t *sbuf[2] = {reinterpret_cast<uint16_t *>(ctx->workspace.as<float>()),
-                       reinterpret_cast<uint16_t *>(ctx->workspace.as<float>() + split_stride)};
-  float *out = ctx->workspace.as<float>() + 2 * split_stride;
-  const uint16_t *xs = nullptr;
-  int px = 0;
-  int cur = 0;
-  for (size_t i = 0; i < m->steps.size(); ++i) {
-    const GemmLayer &g = m->steps[i].gemm;
-    const bool last = i + 1 == m->steps.size();
-    X6Gemm a;
-    if (i == 0) {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
-      CE_TRY(launch_splice_pad_split(ctx->stream, x, ldx, rows, g.din, g.nseg, g.off, row_map, sbuf[cur], g.kpad));
-      xs = sbuf[cur];
-      px = g.kpad;
-      cur ^= 1;
-      a.din = g.kpad;
-      a.nseg = 1;
-    } else {
-      a.din = g.din;
-      a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = g.off[s];
-    }
-    a.x = xs;
-    a.ldx = 3 * px;
-    a.px = px;
-    a.w = g.wsplit.as<uint16_t>();
-    a.ldw = 3 * g.kpad;
-    a.pw = g.kpad;
-    a.m = rows;
-    a.n = g.n;
-    a.kpad = i == 0 ? g.kpad : g.nseg * g.din;
-    a.bias = g.bias.as<float>();
-    a.bn_scale = g.bn_scale.as<float>();
-    a.bn_offset = g.bn_offset.as<float>();
-    for (int q = 0; q < 4; ++q) a.post[q] = g.post[q];
-    a.npost = g.npost;
-    const int pn = (g.n + 31) / 32 * 32;
-    if (last) {
-      a.y32 = out;
-      a.ldy = g.n;
-    } else {
-      a.y16 = sbuf[cur];
-      a.ldy = 3 * pn;
-      a.py = pn;
-    }
-    {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM);
-      CE_TRY(launch_gemm_bf16x6(ctx->stream, a));
-    }
-    xs = sbuf[cur];
-    px = pn;
-    cur ^= 1;
-  }
-  *y = out;
-  *ldy = m->steps.back().gemm.n;
-  return CE_GPU_OK;
-}
-
-// The plain bf16 program (kernels/gemm_bf16.hip, CE_GPU_GEMM_BF16): the first
-// layer's spliced block is written as bf16, every hidden layer's epilogue
-// writes bf16(y) for the next, the last layer writes fp32.  Two ping-pong
-// blocks of rows x max_in bf16 plus the fp32 output: a third of
-// run_steps_x6's planes, so inside what reserve_packed_rows reserves (its
-// max_in rounds widths up to 64, this one to 32) and a session push still
-// allocates nothing.  The context's latency and wide-tile settings are not
-// read: one kernel family, its tile a function of (rows, n).
-static int run_steps_bf16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                          const int *row_map, const float **y, int *ldy, const IncrChunk *inc = nullptr) {
-  int max_in = 0;
-  for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
-  for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 31) / 32 * 32);
-  const size_t blk_floats = ((size_t)rows * max_in + 1) / 2;
-  const size_t blk_stride = (blk_floats + 63) / 64 * 64;
-  CE_TRY(ensure_workspace(ctx, 2 * blk_stride + (size_t)rows * m->num_pdfs));
-  uint16_t *sbuf[2] = {reinterpret_cast<uint16_t *>(ctx->workspace.as<float>()),
-                       reinterpret_cast<uint16_t *>(ctx->workspace.as<float>() + blk_stride)};
-  float *out = ctx->workspace.as<float>() + 2 * blk_stride;
-  const uint16_t *xs = nullptr;
-  int px = 0, cur = 0;
-  for (size_t i = 0; i < m->steps.size(); ++i) {
-    const GemmLayer &g = m->steps[i].gemm;
-    const bool last = i + 1 == m->steps.size();
-    X6Gemm a;
-    int off[8];
-    layer_offsets(g, inc, off);
-    if (i == 0) {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
-      CE_TRY(launch_splice_pad_bf16(ctx->stream, x, ldx, rows, g.din, g.nseg, off, row_map, sbuf[cur], g.kpad));
-      xs = sbuf[cur];
-      px = g.kpad;
-      cur ^= 1;
-      a.din = g.kpad;
-      a.nseg = 1;
-    } else {
-      a.din = g.din;
-      a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = off[s];
-      CE_TRY(exchange_input(ctx, inc, (int)i, xs, (size_t)px * 2, (size_t)px * 2));
-    }
-    a.x = xs;
-    a.ldx = px;
-    a.wd = g.wdir.as<uint16_t>();
-    a.wd_kt = g.kpad / 32;
-    a.m = rows;
-    a.n = g.n;
-    a.kpad = i == 0 ? g.kpad : g.nseg * g.din;
-    a.bias = g.bias.as<float>();
-    a.bn_scale = g.bn_scale.as<float>();
-    a.bn_offset = g.bn_offset.as<float>();
-    for (int q = 0; q < 4; ++q) a.post[q] = g.post[q];
-    a.npost = g.npost;
-    const int pn = (g.n + 31) / 32 * 32;
-    if (last) {
-      a.y32 = out;
-      a.ldy = g.n;
-    } else {
-      a.y16 = sbuf[cur];
-      a.ldy = pn;
-    }
-    {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM);
-      CE_TRY(launch_gemm_bf16(ctx->stream, a));
-    }
-    xs = sbuf[cur];
-    px = pn;
-    cur ^= 1;
-  }
-  *y = out;
-  *ldy = m->steps.back().gemm.n;
-  return CE_GPU_OK;
-}
-
-static int ensure_overflow_word(ce_gpu_ctx *ctx) {
-  if (ctx->overflow.ptr) return CE_GPU_OK;
-  CE_TRY(ctx->overflow.alloc(256));
-  CE_HIP(hipMemsetAsync(ctx->overflow.ptr, 0, 256, ctx->stream));
-  return CE_GPU_OK;
-}
-
-// The f16x3 program (kernels/gemm_f16x3.hip): as run_steps_x6 with two fp16
-// planes per operand; splits beyond the fp16 range set ctx->overflow.
-static int run_steps_x3(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                        const int *row_map, const float **y, int *ldy) {
-  CE_TRY(ensure_overflow_word(ctx));
-  int *overflow = ctx->overflow.as<int>();
-  int max_in = 0;
-  for (const Step &st : m->steps) max_in = std::max(max_in, st.gemm.kpad);
-  for (const Step &st : m->steps) max_in = std::max(max_in, (st.gemm.n + 63) / 64 * 64);
-  // two split ping-pong blocks (rows x 2 x max_in fp16) + the fp32 output
-  const size_t split_floats = (size_t)rows * max_in;
-  const size_t split_stride = (split_floats + 63) / 64 * 64;
-  CE_TRY(ensure_workspace(ctx, 2 * split_stride + (size_t)rows * m->num_pdfs));
-  uint16_t *sbuf[2] = {reinterpret_cast<uint16_t *>(ctx->workspace.as<float>()),
-                       reinterpret_cast<uint16_t *>(ctx->workspace.as<float>() + split_stride)};
-  float *out = ctx->workspace.as<float>() + 2 * split_stride;
-  const uint16_t *xs = nullptr;
-  int px = 0, cur = 0;
-  for (size_t i = 0; i < m->steps.size(); ++i) {
-    const GemmLayer &g = m->steps[i].gemm;
-    const bool last = i + 1 == m->steps.size();
-    X3Gemm a;
-    if (i == 0) {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM_GATHER);
-      CE_TRY(launch_splice_pad_f16(ctx->stream, x, ldx, rows, g.din, g.nseg, g.off, row_map, sbuf[cur], g.kpad,
-                                   overflow));
-      xs = sbuf[cur];
-      px = g.kpad;
-      cur ^= 1;
-      a.din = g.kpad;
-      a.nseg = 1;
-    } else {
-      a.din = g.din;
-      a.nseg = g.nseg;
-      for (int s = 0; s < 8; ++s) a.off[s] = g.off[s];
-    }
-    a.x = xs;
-    a.ldx = 2 * px;
-    a.px = px;
-    a.w = g.wf16.as<uint16_t>();
-    a.ldw = 2 * g.kpad;
-    a.pw = g.kpad;
-    a.m = rows;
-    a.n = g.n;
-    a.kpad = i == 0 ? g.kpad : g.nseg * g.din;
-    a.unscale = ldexpf(1.0f, -(g.w_shift + kF16ActShift));
-    a.bias = g.bias.as<float>();
-    a.bn_scale = g.bn_scale.as<float>();
-    a.bn_offset = g.bn_offset.as<float>();
-    for (int q = 0; q < 4; ++q) a.post[q] = g.post[q];
-    a.npost = g.npost;
-    a.overflow = overflow;
-    const int pn = (g.n + 63) / 64 * 64;
-    if (last) {
-      a.y32 = out;
-      a.ldy = g.n;
-    } else {
-      a.y16 = sbuf[cur];
-      a.ldy = 2 * pn;
-      a.py = pn;
-    }
-    {
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM);
-      CE_TRY(launch_gemm_f16x3(ctx->stream, a));
-    }
-    xs = sbuf[cur];
-    px = pn;
-    cur ^= 1;
-  }
-  *y = out;
-  *ldy = m->steps.back().gemm.n;
-  return CE_GPU_OK;
-}
-
-// The int8 program (kernels/nnet_i8.hip): per Linear layer min/max ->
-// quantize (+ row sums) -> u8 GEMM with float epilogue.
-static int run_steps_i8(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                        const int *row_map, const uint32_t *row_edge, const float **y, int *ldy) {
-  const size_t per = (size_t)rows * m->max_width;
-  CE_TRY(ensure_workspace(ctx, 2 * per));
-  float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
-  int max_ldq = 16;
-  for (const Step &st : m->steps)
-    if (st.is_gemm) max_ldq = std::max(max_ldq, st.i8.spliced ? st.i8.kpad : st.i8.in_width);
-  int max_n = 1;
-  for (const Step &st : m->steps)
-    if (st.is_gemm) max_n = std::max(max_n, st.i8.n);
-  const size_t q_bytes = ((size_t)rows * max_ldq + 255) / 256 * 256;
-  const size_t rs_bytes = ((size_t)rows * 4 + 255) / 256 * 256;
-  const size_t part_bytes = std::max(i8_params_scratch_bytes(), sizeof(float) * 2 * i8_gemm_parts(rows, max_n));
-  CE_TRY(ensure_scratch(ctx, q_bytes + rs_bytes + 256 + part_bytes));
-  char *base = static_cast<char *>(ctx->scratch.ptr);
-  int8_t *xq = reinterpret_cast<int8_t *>(base);
-  int32_t *rowsum = reinterpret_cast<int32_t *>(base + q_bytes);
-  void *params = base + q_bytes + rs_bytes;
-  void *part = base + q_bytes + rs_bytes + 256;
-  int cur = 0;
-  bool first = true;
-  int fused_parts = 0;  // > 0: the previous GEMM left this layer's min / max partials in `part`
-  for (size_t si = 0; si < m->steps.size(); ++si) {
-    const Step &st = m->steps[si];
-    if (st.is_gemm) {
-      const I8Layer &L = st.i8;
-      const int *rm = first ? row_map : nullptr;
-      const int ldq = L.spliced ? L.kpad : L.in_width;
-      {
-        ProfScope prof(ctx, CE_GPU_PROF_QUANT);
-        const int zero[1] = {0};
-        const int nseg = L.spliced ? st.gemm.nseg : 1;
-        const int *offs = L.spliced ? st.gemm.off : zero;
-        if (!(diag_skip() & 64)) {  // measurement library: 64 leaves the int8 quantize passes out
-          if (fused_parts > 0)
-            CE_TRY(launch_i8_params_fold(ctx->stream, part, fused_parts, params));
-          else
-            CE_TRY(launch_i8_params(ctx->stream, x, ldx, rows, L.in_width, rm, row_edge, L.in_left, L.in_right,
-                                    part, params));
-          CE_TRY(launch_i8_quantize(ctx->stream, x, ldx, rows, L.in_width, rm, nseg, offs, params, xq, ldq, rowsum));
-        }
-      }
-      // the next step reads this GEMM's output directly: its min / max is
-      // reduced in this GEMM's epilogue (the partials are read by the next
-      // layer's fold before the next GEMM overwrites them: stream order)
-      const bool fuse = si + 1 < m->steps.size() && m->steps[si + 1].is_gemm && m->steps[si + 1].i8.in_width == L.n;
-      I8NextMinMax mm = {};
-      if (fuse) {
-        const I8Layer &N = m->steps[si + 1].i8;
-        mm = I8NextMinMax{part, row_edge, N.in_left, N.in_right};
-      }
-      fused_parts = 0;
-      ProfScope prof(ctx, CE_GPU_PROF_GEMM);
-      CE_TRY(launch_i8_gemm(ctx->stream, L, xq, ldq, rows, rowsum, params, buf[cur], L.n, fuse ? &mm : nullptr,
-                            fuse ? &fused_parts : nullptr));
-      x = buf[cur];
-      ldx = L.n;
-      cur ^= 1;
-      first = false;
-    } else {
-      fused_parts = 0;
-      CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
-    }
-  }
-  *y = x;
-  *ldy = ldx;
-  return CE_GPU_OK;
-}
-
-// Scratch of the static int8 program for `rows` rows: two operand buffers
-// (a GEMM with the requantize epilogue reads one and writes the other) and
-// three row-sum buffers (read / added into / cleared for the next launch).
-static void i8_static_scratch(const ce_gpu_model *m, int rows, size_t *q_bytes, size_t *rs_bytes) {
-  int max_ldq = 16;
-  for (const Step &st : m->steps)
-    if (st.is_gemm) max_ldq = std::max(max_ldq, st.i8.spliced ? st.i8.kpad : st.i8.in_width);
-  *q_bytes = ((size_t)rows * max_ldq + 255) / 256 * 256;
-  *rs_bytes = ((size_t)rows * 4 + 255) / 256 * 256;
-}
-
-// The static int8 program (ce_gpu_model_quantize_static): every Linear's
-// activation parameters are the model's frozen ones, so nothing is reduced
-// over the block.  A GEMM whose output is the next Linear's plain operand
-// (that layer reads whole 128-byte K-tiles of it) writes that layer's bytes
-// and row sums itself (I8NextBytes); every other layer input goes through the
-// quantize pass with the frozen parameters.  CATEARS_I8_FUSED=0 (experiments
-// library, read per call: tools/i8_static.py) keeps the quantize pass
-// everywhere.
-static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                               const int *row_map, const float **y, int *ldy, const IncrChunk *inc = nullptr) {
-  const size_t per = (size_t)rows * m->max_width;
-  CE_TRY(ensure_workspace(ctx, 2 * per));
-  float *buf[2] = {ctx->workspace.as<float>(), ctx->workspace.as<float>() + per};
-  size_t q_bytes = 0, rs_bytes = 0;
-  i8_static_scratch(m, rows, &q_bytes, &rs_bytes);
-  CE_TRY(ensure_scratch(ctx, 2 * q_bytes + 3 * rs_bytes));
-  char *base = static_cast<char *>(ctx->scratch.ptr);
-  int8_t *xq[2] = {reinterpret_cast<int8_t *>(base), reinterpret_cast<int8_t *>(base + q_bytes)};
-  int32_t *rs[3];
-  for (int i = 0; i < 3; ++i) rs[i] = reinterpret_cast<int32_t *>(base + 2 * q_bytes + i * rs_bytes);
-  const bool fused_ok = CE_KNOB("CATEARS_I8_FUSED", 1) != 0;
-  int cur = 0, qc = 0, rc = 0, linear = 0;
-  bool first = true, have_bytes = false;  // have_bytes: the previous GEMM wrote xq[qc] / rs[rc]
-  for (size_t si = 0; si < m->steps.size(); ++si) {
-    const Step &st = m->steps[si];
-    if (!st.is_gemm) {
-      CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
-      continue;
-    }
-    const I8Layer &L = st.i8;
-    const int ldq = L.spliced ? L.kpad : L.in_width;
-    // an incremental chunk: the cached context joins the layer's input in the
-    // form it has here -- fp32 rows ahead of the quantize pass, or the bytes
-    // and row sums the previous GEMM wrote -- and whichever launch reads that
-    // input through the splice offsets reads it causally
-    int off[8];
-    layer_offsets(st.gemm, inc, off);
-    if (!have_bytes) {
-      CE_TRY(exchange_input(ctx, inc, linear, x, (size_t)L.in_width * 4, (size_t)ldx * 4));
-      ProfScope prof(ctx, CE_GPU_PROF_QUANT);
-      const int zero[1] = {0};
-      CE_TRY(launch_i8_quantize(ctx->stream, x, ldx, rows, L.in_width, first ? row_map : nullptr,
-                                L.spliced ? st.gemm.nseg : 1, L.spliced ? off : zero, L.qp, xq[qc], ldq, rs[rc],
-                                rs[(rc + 1) % 3]));
-    } else {
-      CE_TRY(exchange_input(ctx, inc, linear, xq[qc], (size_t)L.in_width, (size_t)ldq, rs[rc]));
-    }
-    ++linear;
-    const int shift = L.spliced ? 0 : causal_shift(st.gemm, inc);
-    const I8Layer *N = si + 1 < m->steps.size() && m->steps[si + 1].is_gemm ? &m->steps[si + 1].i8 : nullptr;
-    const bool fuse = fused_ok && N && N->in_width == L.n && !N->spliced && i8_gemm_can_requantize(L, ldq);
-    // latency mode: the split-K pair where the slice rule gives it this layer
-    // at this row count (the same bits, and the same row-sum rotation: either
-    // producer reads rs[rc], adds into the cleared rs[rc + 1], clears rs[rc + 2])
-    int lat_slices = 0, lat_per = 0;
-    if (ctx->latency && i8_lat_eligible(L, ldq)) i8_lat_plan(L.kpad, L.n, rows, &lat_slices, &lat_per);
-    size_t lat_words = 0;
-    if (lat_slices > 0) {
-      lat_words = i8_lat_part_words(rows, L.n, lat_slices);
-      CE_TRY(ensure_lat_part(ctx, lat_words));
-    }
-    ProfScope prof(ctx, CE_GPU_PROF_GEMM);
-    if (fuse) {
-      const I8NextBytes nb = {xq[qc ^ 1], rs[(rc + 1) % 3], rs[(rc + 2) % 3], N->qp};
-      if (lat_slices > 0)
-        CE_TRY(launch_i8_lat(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, &nb,
-                             ctx->lat_part.as<int32_t>(), lat_words, shift));
-      else
-        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, nullptr, L.n, nullptr, nullptr, &nb,
-                              shift));
-      qc ^= 1;
-      rc = (rc + 1) % 3;
-      x = nullptr;
-    } else {
-      if (lat_slices > 0)
-        CE_TRY(launch_i8_lat(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n, nullptr,
-                             ctx->lat_part.as<int32_t>(), lat_words, shift));
-      else
-        CE_TRY(launch_i8_gemm(ctx->stream, L, xq[qc], ldq, rows, rs[rc], L.qp, buf[cur], L.n, nullptr, nullptr, nullptr,
-                              shift));
-      x = buf[cur];
-      cur ^= 1;
-    }
-    ldx = L.n;
-    have_bytes = fuse;
-    first = false;
-  }
-  *y = x;
-  *ldy = ldx;
-  return CE_GPU_OK;
-}
-
-static int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
-                     const int *row_map, const uint32_t *row_edge, const float **y, int *ldy,
-                     LatTail *tail = nullptr, CalibTap *tap = nullptr, const IncrChunk *inc = nullptr) {
-  if (tail) tail->active = false;
-  if (inc) {
-    // an incremental session chunk (sessions_create_ex admitted these forms only)
-    if (tap || (m->int8 && !m->int8_static)) return fail(CE_GPU_EINVAL, "incremental chunk: unsupported form");
-    if (m->int8) return run_steps_i8_static(ctx, m, x, ldx, rows, row_map, y, ldy, inc);
-    if (m->gemm == CE_GPU_GEMM_BF16) return run_steps_bf16(ctx, m, x, ldx, rows, row_map, y, ldy, inc);
-    if (m->gemm == CE_GPU_GEMM_BF16X6 && x6_f32in() && x6_plane_chain_env() == 0)
-      return run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail, nullptr, inc);
-    if (m->gemm == CE_GPU_GEMM_FP32) return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy, nullptr, inc);
-    return fail(CE_GPU_ENOTSUP, "incremental chunk: GEMM modes fp32, bf16x6 and bf16 only");
-  }
-  if (tap) {
-    // calibration reads fp32 activations between the layers
-    if (m->int8) return fail(CE_GPU_EINVAL, "model_calibrate: the model is already quantized");
-    if (m->gemm == CE_GPU_GEMM_BF16X6 && x6_f32in() && x6_plane_chain_env() == 0)
-      return run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, nullptr, tap);
-    if (m->gemm == CE_GPU_GEMM_FP32) return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy, tap);
-    return fail(CE_GPU_ENOTSUP, "model_calibrate: GEMM modes fp32 and bf16x6 only (the others keep activations as planes)");
-  }
-  if (m->int8 && m->int8_static) return run_steps_i8_static(ctx, m, x, ldx, rows, row_map, y, ldy);
-  if (m->int8) return run_steps_i8(ctx, m, x, ldx, rows, row_map, row_edge, y, ldy);
-  if (m->gemm == CE_GPU_GEMM_F16X3) return run_steps_x3(ctx, m, x, ldx, rows, row_map, y, ldy);
-  if (m->gemm == CE_GPU_GEMM_BF16) return run_steps_bf16(ctx, m, x, ldx, rows, row_map, y, ldy);
-  if (m->gemm == CE_GPU_GEMM_BF16X6_PLANES) return run_steps_x6(ctx, m, x, ldx, rows, row_map, y, ldy);
-  if (m->gemm == CE_GPU_GEMM_BF16X6)
-    return x6_f32in() ? run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail)
-                      : run_steps_x6(ctx, m, x, ldx, rows, row_map, y, ldy);
-  return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy);
-}
-
-// The latency GEMM may defer its last layer's reduce into the finalize only
-// when the fused finalize can write the caller's output: it stores 16-byte
-// row chunks (launch_lat_finalize), so out and the log prior must be 16-byte
-// aligned.  Otherwise the layer keeps its own reduce launch and the ordinary
-// finalize (scalar path for unaligned rows) runs -- decided before any GEMM
-// is launched.
-static bool lat_tail_ok(const float *out, const float *log_prior) {
-  return ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(log_prior)) & 15) == 0;
-}
-
-// launch_finalize on rows first .. first + rows - 1 of run_steps' output
-// (or of its deferred latency tail: the last layer's reduce in the same
-// launch)
-static int finalize_output(ce_gpu_ctx *ctx, const float *y, int ldy, int first, int rows, int dim,
-                           bool log_softmax, const float *log_prior, const int *row_dst, float *out,
-                           const LatTail &tail = LatTail()) {
-  if (diag_skip() & 2) return CE_GPU_OK;
-  if (tail.active) return launch_lat_finalize(ctx->stream, tail, first, rows, log_softmax, log_prior, row_dst, out);
-  return launch_finalize(ctx->stream, y + (size_t)first * ldy, ldy, rows, dim, log_softmax, log_prior, row_dst,
-                         out);
-}
-
-// Quantize (src/matrix.cc:329-387) of one weight matrix on the host at load
-// time: per-tensor parameters over the in x out MAT0 matrix, then the bytes
-// stored shifted (q - 128) and transposed (n x kpad, zero padded) for the
-// GEMM, with their column sums.
-static int quantize_weights(ce_gpu_ctx *ctx, Step &st) {
-  GemmLayer &g = st.gemm;
-  I8Layer &L = st.i8;
-  std::vector<float> wt((size_t)g.n * g.kpad);
-  CE_HIP(hipMemcpy(wt.data(), g.wt.ptr, wt.size() * 4, hipMemcpyDeviceToHost));
-  float mn = FLT_MAX, mx = FLT_MIN;  // FindMinMax (matrix.cc:329-345)
-  for (int j = 0; j < g.n; ++j)
-    for (int k = 0; k < g.k; ++k) {
-      const float v = wt[(size_t)j * g.kpad + k];
-      if (v > mx) mx = v;
-      if (v < mn) mn = v;
-    }
-  const double scale = (mx - mn) / 255.0;  // ComputeQuantizationParams (matrix.cc:348-362)
-  L.w_zp = (int32_t)round(-mn / scale);
-  L.w_scale = (float)scale;
-  const int ka = i8_k_align();
-  L.n = g.n;
-  L.k = g.k;
-  L.kpad = (g.k + ka - 1) / ka * ka;
-  std::vector<int8_t> q((size_t)g.n * L.kpad, 0);
-  std::vector<int32_t> colsum(g.n, 0);
-  for (int j = 0; j < g.n; ++j)
-    for (int k = 0; k < g.k; ++k) {
-      float v = wt[(size_t)j * g.kpad + k] / L.w_scale + L.w_zp;  // matrix.cc:378-386
-      v = std::max(0.0f, std::min(v, 255.0f));
-      const int b = (int)(uint8_t)roundf(v) - 128;
-      q[(size_t)j * L.kpad + k] = (int8_t)b;
-      colsum[j] += b;
-    }
-  CE_TRY(L.wq.upload(q.data(), q.size()));
-  CE_TRY(L.colsum.upload(colsum.data(), colsum.size() * 4));
-  L.in_width = g.din;
-  L.in_left = g.in_left;
-  L.in_right = g.in_right;
-  L.spliced = g.din % ka != 0;
-  if (L.spliced) {
-    L.a_din = L.kpad;
-    L.a_nseg = 1;
-    for (int i = 0; i < 8; ++i) L.a_off[i] = 0;
-  } else {
-    L.a_din = g.din;
-    L.a_nseg = g.nseg;
-    for (int i = 0; i < 8; ++i) L.a_off[i] = g.off[i];
-  }
-  L.bias = g.bias.as<float>();
-  L.bn_scale = g.bn_scale.as<float>();
-  L.bn_offset = g.bn_offset.as<float>();
-  for (int i = 0; i < 4; ++i) L.post[i] = g.post[i];
-  L.npost = g.npost;
-  (void)ctx;
-  return CE_GPU_OK;
-}
-
-int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats, int rows, const int *row_src,
-                      const uint32_t *row_edge, const int *row_dst, float *d_loglik, const IncrChunk *inc) {
-  const float *y = nullptr;
-  int ldy = 0;
-  LatTail tail;
-  CE_TRY(run_steps(ctx, m, feats, m->input_dim, rows, row_src, row_edge, &y, &ldy,
-                   lat_tail_ok(d_loglik, m->log_prior.as<float>()) ? &tail : nullptr, nullptr, inc));
-  ProfScope prof(ctx, CE_GPU_PROF_FINALIZE);
-  return finalize_output(ctx, y, ldy, 0, rows, m->num_pdfs, m->final_log_softmax, m->log_prior.as<float>(), row_dst,
-                         d_loglik, tail);
-}
-
-// The sizes below are the ones run_steps_f32 / _x6f / _x6 / _x3 ask the
-// ensure_* calls for; the largest of them covers every mode the model can be
-// switched to later.
-int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows) {
-  if (m->int8 && !m->int8_static) return fail(CE_GPU_ENOTSUP, "reserve_packed_rows: int8 model");
-  if (m->int8_static) {
-    // what run_steps_i8_static asks for
-    size_t q_bytes = 0, rs_bytes = 0;
-    i8_static_scratch(m, rows, &q_bytes, &rs_bytes);
-    CE_TRY(ensure_workspace(ctx, 2 * (size_t)rows * m->max_width));
-    CE_TRY(ensure_scratch(ctx, 2 * q_bytes + 3 * rs_bytes));
-    // the latency pair's partials: the slice rule depends on the row count,
-    // so the largest over every count a later call may bring
-    size_t lat = 0;
-    for (const Step &st : m->steps) {
-      if (!st.is_gemm || !i8_lat_eligible(st.i8, st.i8.spliced ? st.i8.kpad : st.i8.in_width)) continue;
-      for (int r = 1; r <= std::min(rows, kI8LatMaxRows); ++r) {
-        int slices = 0, per = 0;
-        i8_lat_plan(st.i8.kpad, st.i8.n, r, &slices, &per);
-        lat = std::max(lat, i8_lat_part_words(r, st.i8.n, slices));
-      }
-    }
-    return lat ? ensure_lat_part(ctx, lat) : CE_GPU_OK;
-  }
-  const size_t r = (size_t)rows;
-  size_t ws = 2 * r * m->max_width, scratch = 0, lat = 0;
-  int max_in = 0;
-  bool all_gemm = true;
-  for (const Step &st : m->steps) {
-    if (!st.is_gemm) {
-      all_gemm = false;
-      continue;
-    }
-    const GemmLayer &g = st.gemm;
-    max_in = std::max(max_in, std::max(g.kpad, (g.n + 63) / 64 * 64));
-    if (g.din % 32 != 0) scratch = std::max(scratch, r * g.kpad * sizeof(float));
-  }
-  if (m->x6_ok && all_gemm) {
-    // three bf16 planes (1.5 floats per element) cover the fp32 chain, the
-    // two fp16 planes and the plain bf16 mode's single one (run_steps_bf16)
-    // as well
-    const size_t blk = (r * max_in * 3 / 2 + 1 + 63) / 64 * 64;
-    ws = std::max(ws, 2 * blk + r * m->num_pdfs);
-    for (size_t i = 0; i < m->steps.size(); ++i) {
-      const GemmLayer &g = m->steps[i].gemm;
-      const int kpad = i == 0 ? g.kpad : g.nseg * g.din;
-      if (kpad % 32 == 0) lat = std::max(lat, x6_lat_part_floats(rows, g.n, x6_lat_slices(kpad, g.n)));
-    }
-    CE_TRY(ensure_overflow_word(ctx));
-  }
-  CE_TRY(ensure_workspace(ctx, ws));
-  if (scratch) CE_TRY(ensure_scratch(ctx, scratch));
-  if (lat) CE_TRY(ensure_lat_part(ctx, lat));
-  return CE_GPU_OK;
-}
-}  // namespace catears
-
-extern "C" {
 
 int ce_gpu_am_forward(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_plan *p, const float *d_feats,
                       float *d_loglik) {

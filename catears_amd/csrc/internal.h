@@ -660,7 +660,7 @@ int launch_gemm_u8_ws(hipStream_t s, int m, int n, int k, const uint8_t *a, cons
 
 // ---- device-resident sessions (sessions.cc, kernels/sessions.hip) ----
 
-// One chunk of packed rows through the nnet and the finalize (capi.cc, what
+// One chunk of packed rows through the nnet and the finalize (nnet_programs.cc, what
 // ce_gpu_am_forward runs per plan chunk): packed row r reads feature row
 // row_src[r] of feats (input_dim wide) and, when row_dst[r] >= 0, becomes row
 // row_dst[r] of d_loglik.

@@ -404,6 +404,84 @@ def test_no_allocation_once_warm(torch, G, ctx, model, gs):
     check_jobs(torch, G, ctx, model, gs, jobs, got)
 
 
+def test_reserve_covers_every_mode(torch, G, xs_config, gs):
+    """One set created with the model in its default mode, then the model
+    switched through every GEMM mode with the context's latency mode off and
+    on: the workspaces grown at create cover all of them, so the allocation
+    and release counts stand still from the first mode's second tick to the
+    last mode's last one, and every mode's rows are its one-shot rows.  The
+    references are computed afterwards: a one-shot call before would size the
+    context's workspaces itself."""
+    from catears_amd import synth
+    c = G.Context(0)
+    m = G.Model(c, xs_config)
+    waves = [synth.pcm(1000 + s, 4 * 1600) for s in range(2)]
+    pcm = [dev(torch, w) for w in waves]
+    configs = [(lat, mode) for lat in (False, True) for mode in ("fp32", "bf16x6", "bf16x6p", "f16x3", "bf16")]
+    got, seen = {}, []
+    sess = G.Sessions(c, m, 2, 1600, gs)
+    try:
+        for lat, mode in configs:
+            c.set_latency(lat)
+            m.set_gemm(mode)
+            pieces = [[], []]
+            for t in range(4):
+                order = [t % 2, 1 - t % 2]
+                out, rows = sess.push(order, torch.cat([pcm[s][1600 * t:1600 * (t + 1)] for s in order]), [1600, 1600],
+                                      eos=[t == 3] * 2)
+                host = out.cpu().numpy()
+                pieces[order[0]].append(host[:rows[0]])
+                pieces[order[1]].append(host[rows[0]:])
+                seen.append(G.debug_counters())
+            got[lat, mode] = [np.concatenate(p) for p in pieces]
+            for s in range(2):
+                sess.reset(s)
+    finally:
+        sess.close()
+    assert len(seen) == 4 * len(configs) and seen[1] == seen[-1], (seen[1], seen[-1])
+    assert seen[1][0] > 0
+    for lat, mode in configs:
+        c.set_latency(lat)
+        m.set_gemm(mode)
+        for s in range(2):
+            assert same(got[lat, mode][s], one_shot(torch, G, c, m, waves[s], gs)), (lat, mode, s)
+
+
+def test_reserve_covers_static_int8_latency_row_counts(torch, G, ctx, xs_config, gs):
+    """A static int8 model on a latency-mode context: the split-K pair's slice
+    rule, and with it the partials a push needs, depends on the packed row
+    count.  Pushes that pack 21, 70, 81 and 40 rows allocate nothing after
+    the first, and take the split-K pair."""
+    from catears_amd import synth
+    # calibrated on the module's context, so that nothing but the set's create
+    # sizes the workspaces of the context the pushes run on
+    cal = G.Model(ctx, xs_config)
+    cal_waves = [synth.pcm(1010 + i, 16000) for i in range(2)]
+    plan = G.Plan(ctx, [len(w) for w in cal_waves], cal)
+    ranges = cal.calibrate(ctx, plan, G.fbank(ctx, plan, dev(torch, np.concatenate(cal_waves))))
+    c = G.Context(0)
+    c.set_latency(True)
+    m = G.Model(c, xs_config).quantize_static(c, ranges)
+    counts = [2000, 8000, 9760, 1600]  # 11, 50, 61 and 10 frames: 1, 50, 61 and 20 rows
+    assert G.Sessions.packed_rows(L, R, 0, counts, 3, False) == [21, 70, 81, 40]
+    wave = synth.pcm(1012, sum(counts))
+    sess = G.Sessions(c, m, 1, max(counts), gs)
+    seen = []
+    lat0 = G.debug_i8_latency_launches()
+    try:
+        pcm, at, pieces = dev(torch, wave), 0, []
+        for i, n in enumerate(counts):
+            out, _ = sess.push([0], pcm[at:at + n], [n], eos=[i == 3])
+            pieces.append(out.cpu().numpy())
+            seen.append(G.debug_counters())
+            at += n
+    finally:
+        sess.close()
+    assert seen[0] == seen[-1], seen
+    assert G.debug_i8_latency_launches() > lat0
+    assert same(np.concatenate(pieces), one_shot(torch, G, c, m, wave, gs))
+
+
 # ------------------------------------------------------------- 10. capacity --
 
 def test_capacity_too_small_changes_nothing(torch, G, ctx, model, gs):
