@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float *__restrict__ x
     if (dl < in_left || dr < in_right) continue;
     const int src = row_map ? row_map[r] : r;
     const float *xr = x + (int64_t)src * ldx;
-    if ((width & 3) == 0 && (ldx & 3) == 0) {
+    // float4 rows: also a base on 16 bytes (a caller's block may start at any float)
+    if ((width & 3) == 0 && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
       for (int c = 4 * lane; c < width; c += 256) {
         const float4 v = *reinterpret_cast<const float4 *>(xr + c);
         const float e[4] = {v.x, v.y, v.z, v.w};
@@ -167,7 +168,7 @@ __device__ __forceinline__ void quantize_row(const float *__restrict__ x, int ld
   int8_t *o = q + (int64_t)r * ldq;
   int32_t s = 0;
   const float rs = qbyte_rscale(scale);
-  const bool vec = (width & 3) == 0 && (ldx & 3) == 0;
+  const bool vec = (width & 3) == 0 && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   for (int seg = 0; seg < nseg; ++seg) {
     int src = r + so.off[seg];
     src = src < 0 ? 0 : (src > rows - 1 ? rows - 1 : src);
@@ -1299,7 +1300,7 @@ int launch_i8_quantize(hipStream_t s, const float *x, int ldx, int rows, int wid
   // library): 0 = quantize_kernel, 2 = two rows per wave (+2.1 %).
   static const int qfast = CE_KNOB("CATEARS_I8_QFAST", 1);
   const bool plain = nseg == 1 && !row_map && so.off[0] == 0 && width % 4 == 0 && ldx % 4 == 0 && ldq % 4 == 0 &&
-                     (reinterpret_cast<uintptr_t>(q) & 3) == 0;
+                     (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 3) == 0;
   if (rows > 0 && plain && qfast == 1) {
     hipLaunchKernelGGL(quantize_fast_kernel<1>, dim3((rows + 3) / 4), dim3(256), 0, s, x, ldx, rows, width,
                        static_cast<const QP *>(params), q, ldq, rowsum, zero);

@@ -70,14 +70,24 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float *__restrict__
   }
 }
 
-// The same with 16-byte accesses (dim, ldx multiples of 4, aligned rows),
-// one 256-thread block per row: thread t holds float4 chunks t, t + 256, ...
-// of its row (up to 4096 wide), everything loaded up front; the exp sum is
-// per thread in chunk order, then per wave (xor tree), then the four waves'
-// sums in wave order.  A function of the row alone, not of the row count.
+// Rows of whole float4 chunks (dim a multiple of 4, up to 4096), one
+// 256-thread block per row: thread t holds chunks t, t + 256, ... of its row,
+// everything loaded up front; the exp sum is per thread in chunk order, then
+// per wave (xor tree), then the four waves' sums in wave order.  A function of
+// the row alone, not of the row count -- and not of where the caller's buffers
+// lie: VEC moves each chunk with one 16-byte access (ldx a multiple of 4,
+// every base 16-byte aligned), !VEC with four 4-byte ones, the arithmetic and
+// its order the same, so an output at any float carries the same bits (as
+// does latency mode's fused tail, which keeps this order too).
 constexpr int kMaxVecPerThread = 4;
 
-template <bool LOGSM>
+template <bool VEC>
+__device__ __forceinline__ float4 load_chunk(const float *p) {
+  if constexpr (VEC) return *reinterpret_cast<const float4 *>(p);
+  return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+template <bool LOGSM, bool VEC>
 __global__ __launch_bounds__(256) void finalize_vec_kernel(const float *__restrict__ x, int ldx, int rows, int dim,
                                                            const float *__restrict__ prior,
                                                            const int *__restrict__ row_dst,
@@ -86,17 +96,16 @@ __global__ __launch_bounds__(256) void finalize_vec_kernel(const float *__restri
   const int row = blockIdx.x, t = threadIdx.x;
   const int dst = row_dst ? row_dst[row] : row;
   if (dst < 0) return;
-  const float4 *xr = reinterpret_cast<const float4 *>(x + (int64_t)row * ldx);
-  const float4 *pr = reinterpret_cast<const float4 *>(prior);
-  float4 *o = reinterpret_cast<float4 *>(out + (int64_t)dst * dim);
+  const float *xr = x + (int64_t)row * ldx;
+  float *o = out + (int64_t)dst * dim;
   const int d4 = dim >> 2;
   float4 v[kMaxVecPerThread], pv[kMaxVecPerThread];
   float s = 0.0f;
 #pragma unroll
   for (int j = 0; j < kMaxVecPerThread; ++j) {
     const int c = min(t + 256 * j, d4 - 1);  // clamped: loads branch-free, used only when in range
-    v[j] = xr[c];
-    if (prior) pv[j] = pr[c];
+    v[j] = load_chunk<VEC>(xr + 4 * c);
+    if (prior) pv[j] = load_chunk<VEC>(prior + 4 * c);
   }
   if (LOGSM) {
 #pragma unroll
@@ -115,7 +124,14 @@ __global__ __launch_bounds__(256) void finalize_vec_kernel(const float *__restri
       float4 y = v[j];
       if (LOGSM) y = make_float4(y.x - ls, y.y - ls, y.z - ls, y.w - ls);
       if (prior) y = make_float4(y.x - pv[j].x, y.y - pv[j].y, y.z - pv[j].z, y.w - pv[j].w);
-      o[c] = y;
+      if constexpr (VEC) {
+        *reinterpret_cast<float4 *>(o + 4 * c) = y;
+      } else {
+        o[4 * c] = y.x;
+        o[4 * c + 1] = y.y;
+        o[4 * c + 2] = y.z;
+        o[4 * c + 3] = y.w;
+      }
     }
   }
 }
@@ -228,16 +244,14 @@ int launch_finalize(hipStream_t s, const float *x, int ldx, int rows, int dim, b
                     const float *log_prior, const int *row_dst, float *out) {
   if (rows <= 0) return CE_GPU_OK;
   dim3 grid((rows + 3) / 4), block(256);
-  const bool vec = dim % 4 == 0 && ldx % 4 == 0 && dim <= 4 * 256 * kMaxVecPerThread &&
-                   ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) |
-                     reinterpret_cast<uintptr_t>(log_prior)) & 15) == 0;
-  if (vec) {
-    if (log_softmax)
-      hipLaunchKernelGGL(finalize_vec_kernel<true>, dim3(rows), block, 0, s, x, ldx, rows, dim, log_prior, row_dst,
-                         out);
-    else
-      hipLaunchKernelGGL(finalize_vec_kernel<false>, dim3(rows), block, 0, s, x, ldx, rows, dim, log_prior, row_dst,
-                         out);
+  // whole float4 chunks per row: one kernel and one summation order, with
+  // 16-byte accesses where the caller's buffers allow them
+  if (dim % 4 == 0 && dim <= 4 * 256 * kMaxVecPerThread) {
+    const bool vec = ldx % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) |
+                                       reinterpret_cast<uintptr_t>(log_prior)) & 15) == 0;
+    auto kernel = log_softmax ? (vec ? finalize_vec_kernel<true, true> : finalize_vec_kernel<true, false>)
+                              : (vec ? finalize_vec_kernel<false, true> : finalize_vec_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(rows), block, 0, s, x, ldx, rows, dim, log_prior, row_dst, out);
     CE_HIP(hipGetLastError());
     return CE_GPU_OK;
   }

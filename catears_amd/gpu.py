@@ -156,6 +156,18 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _ptr_rows(t):
+    """Device pointer of a matrix argument that travels with its leading
+    dimension (t.stride(0)): a 2-D device tensor whose rows are dense
+    (stride(1) == 1) and do not overlap (stride(0) >= shape[1]).  The view may
+    start at any element of its storage: the C-ABI asks for no alignment."""
+    if t is None:
+        return None
+    if not t.is_cuda or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        raise ValueError("expected a 2-D device tensor with dense rows (stride(1) == 1, stride(0) >= shape[1])")
+    return ctypes.c_void_p(t.data_ptr())
+
+
 class Context:
     """One device + one stream (defaults to torch's current stream)."""
 
@@ -645,7 +657,7 @@ def nnet_propagate(ctx, model, x, subtract_prior=False, out=None):
     rows = x.shape[0]
     if out is None:
         out = torch.empty((max(rows - net_l - net_r, 0), model.num_pdfs), dtype=torch.float32, device=x.device)
-    check(lib().ce_gpu_nnet_propagate(ctx.h, model.h, _ptr(x), rows, x.stride(0), int(subtract_prior), _ptr(out)))
+    check(lib().ce_gpu_nnet_propagate(ctx.h, model.h, _ptr_rows(x), rows, x.stride(0), int(subtract_prior), _ptr(out)))
     return out
 
 
@@ -656,7 +668,7 @@ def nnet_propagate_blocks(ctx, model, x, block_rows, subtract_prior=False, out=N
     n_out = int(rows.sum()) - len(rows) * (model.left + model.right)
     if out is None:
         out = torch.empty((n_out, model.num_pdfs), dtype=torch.float32, device=x.device)
-    check(lib().ce_gpu_nnet_propagate_blocks(ctx.h, model.h, _ptr(x), x.stride(0),
+    check(lib().ce_gpu_nnet_propagate_blocks(ctx.h, model.h, _ptr_rows(x), x.stride(0),
                                              rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(rows),
                                              int(subtract_prior), _ptr(out)))
     return out
@@ -670,7 +682,7 @@ def loglik_gather(ctx, loglik, tid2pdf, rows, trans, am_scale=1.0, out=None):
     assert trans.numel() == n and rows.dtype == trans.dtype == tid2pdf.dtype == torch.int32
     if out is None:
         out = torch.empty((n,), dtype=torch.float32, device=loglik.device)
-    check(lib().ce_gpu_loglik_gather(ctx.h, _ptr(loglik), loglik.shape[0], loglik.stride(0), loglik.shape[1],
+    check(lib().ce_gpu_loglik_gather(ctx.h, _ptr_rows(loglik), loglik.shape[0], loglik.stride(0), loglik.shape[1],
                                      _ptr(tid2pdf),
                                      int(tid2pdf.numel()), _ptr(rows), _ptr(trans), n, float(am_scale),
                                      _ptr(out)))
@@ -683,7 +695,7 @@ def loglik_columns(ctx, loglik, cols, out=None):
     assert cols.dtype == torch.int32
     if out is None:
         out = torch.empty((loglik.shape[0], int(cols.numel())), dtype=torch.float32, device=loglik.device)
-    check(lib().ce_gpu_loglik_columns(ctx.h, _ptr(loglik), loglik.shape[0], loglik.stride(0), loglik.shape[1],
+    check(lib().ce_gpu_loglik_columns(ctx.h, _ptr_rows(loglik), loglik.shape[0], loglik.stride(0), loglik.shape[1],
                                       _ptr(cols), int(cols.numel()), _ptr(out)))
     return out
 
@@ -731,15 +743,55 @@ def sgemm(ctx, a, b, c=None):
     n = b.shape[1]
     if c is None:
         c = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    check(lib().ce_gpu_sgemm(ctx.h, m, n, k, _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c),
+    check(lib().ce_gpu_sgemm(ctx.h, m, n, k, _ptr_rows(a), a.stride(0), _ptr_rows(b), b.stride(0), _ptr_rows(c),
                              c.stride(0)))
     return c
 
 
-def quantize(ctx, x):
-    """Returns (uint8 tensor, 8-byte device params tensor {f32 scale, i32 zp})."""
+ROW_OPS = {"relu": 0, "batchnorm": 1, "log_softmax": 2, "softmax": 3, "normalize": 4}  # CE_GPU_ROW_*
+
+
+def linear(ctx, x, w, bias=None, out=None):
+    """ce_gpu_linear: x (rows, in_dim) @ w (in_dim, out_dim) + bias, each
+    matrix with its own leading dimension."""
     import torch
-    q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    rows, in_dim = x.shape
+    out_dim = w.shape[1]
+    assert w.shape[0] == in_dim
+    if out is None:
+        out = torch.empty((rows, out_dim), dtype=torch.float32, device=x.device)
+    check(lib().ce_gpu_linear(ctx.h, rows, in_dim, out_dim, _ptr_rows(x), x.stride(0), _ptr_rows(w), w.stride(0),
+                              _ptr(bias), _ptr_rows(out), out.stride(0)))
+    return out
+
+
+def splice(ctx, x, indices, out=None):
+    """ce_gpu_splice: row r of the result is x[clamp(r + i)] for i in
+    `indices`, side by side (the reference's clamped Splice); dense output."""
+    import torch
+    rows, dim = x.shape
+    idx = np.ascontiguousarray(indices, np.int32)
+    if out is None:
+        out = torch.empty((rows, dim * len(idx)), dtype=torch.float32, device=x.device)
+    check(lib().ce_gpu_splice(ctx.h, rows, dim, _ptr_rows(x), x.stride(0),
+                              idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx), _ptr(out)))
+    return out
+
+
+def rowwise(ctx, op, x, scale=None, offset=None):
+    """ce_gpu_rowwise in place on the rows of x; op: a ROW_OPS name."""
+    check(lib().ce_gpu_rowwise(ctx.h, ROW_OPS[op], x.shape[0], x.shape[1], _ptr_rows(x), x.stride(0), _ptr(scale),
+                               _ptr(offset)))
+    return x
+
+
+def quantize(ctx, x, q=None):
+    """Returns (uint8 tensor, 8-byte device params tensor {f32 scale, i32 zp});
+    `q`: a contiguous uint8 device tensor of x's element count to write into."""
+    import torch
+    if q is None:
+        q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    assert q.dtype == torch.uint8 and q.numel() == x.numel()
     prm = torch.empty(2, dtype=torch.int32, device=x.device)
     check(lib().ce_gpu_quantize(ctx.h, _ptr(x), x.numel(), _ptr(q), _ptr(prm)))
     return q, prm

@@ -15,6 +15,15 @@
  * device work is enqueued on the context's stream (asynchronous) unless a
  * function says otherwise.
  *
+ * No entry asks more of a device pointer than its element's alignment (4
+ * bytes for float / int32, 1 for uint8) or more of a leading dimension than
+ * ld >= the row's width: a matrix may be a strided view into the middle of a
+ * larger allocation.  Aligned, dense rows are faster; no entry writes
+ * outside the rows it is given, and the nnet entries (nnet_propagate,
+ * nnet_propagate_blocks, am_forward) give the same bits wherever their input
+ * and output lie (tests/test_gpu_caller_buffers.py).  ce_gpu_sum_f64 alone
+ * documents an order that depends on the alignment.
+ *
  * Reference interfaces replaced (all paths relative to the reference root):
  *   Fbank::Process            src/fbank.h:57-59,  src/fbank.cc:265-314
  *   CMVN::CMVN / GetFrame     src/cmvn.h:22-26,   src/cmvn.cc:100-119

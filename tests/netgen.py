@@ -278,13 +278,18 @@ GEOMETRIES = {
     "G20": (40, [640, 3456], [S5, [0]], [("batchnorm",), RB]),
     # two Linears of B with every operand one fp16 plane: the f16x3 recipe
     "B2": (40, [32, 36], [[0], [0]], [RB, ("batchnorm",)]),
+    # a first layer whose segments are whole K-tiles (64 wide): the fp32
+    # program hands the caller's own pointer and row stride to the GEMM, the
+    # bf16x6 program reads the caller's rows through the splice offsets in the
+    # generic direct-weight kernel (no `first` gather form)
+    "H": (64, [96, 64, 36], [[-2, 0, 1], [-1, 0, 1], [0]], [RB, BR, ()]),
 }
 
 ROWS = (1, 17, 70, 129)
 BIG_ROWS = 3000
 BIG = ("A", "D", "G9", "G25", "G20")   # reach the 512 x 128 kernel only there
 BINADE = ("A", "C")                    # +-60-binade variants
-TWO_PLANE_GEOMS = ("A", "B", "C")      # also run with the TWO_PLANES recipe
+TWO_PLANE_GEOMS = ("A", "B", "C", "H") # also run with the TWO_PLANES recipe
 
 
 def max_rows(geom):
@@ -350,11 +355,15 @@ def finalize_path(n):
     return "loop" if n > 4096 else ("vector" if n % 4 == 0 else "scalar")
 
 
-def kernels(layers, out_rows, mode):
+def kernels(layers, out_rows, mode, caller_aligned=True):
     """Per Linear the kernel `mode` runs on a block of out_rows output rows
     (the GEMMs see out_rows + left + right rows); mode: fp32, bf16x6,
     bf16x6p, wide, latency.  A net that is not x6_ok runs the fp32 program
-    whatever was asked."""
+    whatever was asked.  caller_aligned: the caller's rows are float4 rows
+    (16-byte aligned base, ld_in % 4 == 0); without it no kernel reads them
+    with 16-byte loads: the bf16x6 / latency first layer goes through
+    splice_pad (run_steps_x6f's lat_direct) and an fp32 first layer of whole
+    K-tiles leaves the LDS-DMA kernel for pipe2 (launch_gemm_f32's a_fast)."""
     left, right = context(layers)
     m = out_rows + left + right
     ok = x6_ok(layers)
@@ -364,13 +373,17 @@ def kernels(layers, out_rows, mode):
         if mode == "fp32" or not ok:
             # segments that are not whole K-tiles: the spliced block is written
             # once, zero padded, and the same kernel runs on it
-            names.append(("" if g["din"] % 32 == 0 else "splice_pad+") + "f32_glds")
+            if g["din"] % 32 != 0:
+                names.append("splice_pad+f32_glds")
+            else:
+                names.append("f32_glds" if i > 0 or caller_aligned else "f32_pipe2")
             continue
         ktiles = (k64 if i == 0 else g["k"]) // 32
         if mode == "bf16x6p":
             names.append(("splice_pad_split+" if i == 0 else "") + f"x6q_128x128[kt={ktiles}]")
             continue
-        gathered = i == 0 and g["din"] % 8 == 0   # the loader splices the caller's rows itself
+        # the loader splices the caller's rows itself (lat_direct)
+        gathered = i == 0 and g["din"] % 8 == 0 and caller_aligned
         pad = "splice_pad+" if i == 0 and not gathered else ""
         if mode == "latency":
             sl = lat_slices(ktiles, g["n"])

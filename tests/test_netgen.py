@@ -155,5 +155,42 @@ def test_geometries_reach_their_paths():
     assert K(_net("G25"), 70, "latency")[1] == "lat_gemm<KT=8>[7,7,7,4]+lat_finalize"
     assert K(_net("G20"), 70, "latency")[1] == "lat_gemm<KT=6>[5,5,5,5]+lat_finalize"
     assert K(_net("G25"), 3000, "bf16x6")[1] == "x6w_512x128[kt=25]"
+    # H: first-layer segments of two whole K-tiles: no splice_pad in any
+    # program, the caller's rows reach the fp32 LDS-DMA kernel and the generic
+    # (not `first`) direct-weight kernel through the splice offsets
+    h = _net("H")
+    assert netgen.x6_ok(h) and netgen.linears(h)[0]["din"] == 64 and netgen.linears(h)[0]["nseg"] == 3
+    assert K(h, 70, "fp32") == ["f32_glds"] * 3
+    assert K(h, 70, "bf16x6") == ["x6d_256x128[kt=6]", "x6d_256x128[kt=9]", "x6d_256x128[kt=2]"]
+    assert K(h, 70, "latency") == ["lat_gemm<KT=2>[1,1,1,1,1,1]+lat_reduce",
+                                   "lat_gemm<KT=2>[1,1,1,1,1,1,1,1,1]+lat_reduce", "lat_gemm<KT=2>[1,1]+lat_finalize"]
     # the shapes the existing models already cover give the rule's known answers
     assert netgen.lat_slices(32, 1024) == [2] * 16 and netgen.lat_slices(96, 1024) == [6] * 16
+
+
+def test_unaligned_caller_rows_leave_the_fast_paths():
+    """A caller's block that is not made of float4 rows (base off 16 bytes, or
+    ld_in % 4 != 0; netgen.kernels' caller_aligned=False): the bf16x6 and
+    latency first layers that gather the caller's rows go through splice_pad
+    instead, a whole-K-tile fp32 first layer leaves the LDS-DMA kernel; the
+    programs that pad anyway, and every later layer, stay as they are."""
+    def K(geom, mode):
+        return netgen.kernels(_net(geom), 70, mode, caller_aligned=False)
+
+    assert K("A", "bf16x6") == ["splice_pad+x6d_256x128[kt=8]", "x6d_256x128[kt=9]", "x6d_256x128[kt=25]"]
+    assert K("C", "bf16x6") == ["splice_pad+x6d_256x128[kt=6]", "x6d_256x128[kt=24]", "x6d_256x128[kt=2]"]
+    assert K("H", "bf16x6") == ["splice_pad+x6d_256x128[kt=6]", "x6d_256x128[kt=9]", "x6d_256x128[kt=2]"]
+    assert K("A", "wide")[0] == "splice_pad+x6d_128x128[kt=8]"
+    assert K("A", "latency")[0] == "splice_pad+lat_gemm<KT=2>[1,1,1,1,1,1,1,1]+lat_reduce"
+    assert K("C", "latency")[0] == "splice_pad+lat_gemm<KT=2>[1,1,1,1,1,1]+lat_reduce"
+    assert K("H", "latency")[0] == "splice_pad+lat_gemm<KT=2>[1,1,1,1,1,1]+lat_reduce"
+    assert K("H", "fp32") == ["f32_pipe2", "f32_glds", "f32_glds"]
+    assert K("A", "fp32") == ["splice_pad+f32_glds", "f32_glds", "f32_glds"]
+    for geom in ("A", "C", "H"):
+        for mode in ("bf16x6", "wide", "latency"):
+            assert K(geom, mode)[1:] == netgen.kernels(_net(geom), 70, mode)[1:]
+    for geom in ("D", "E"):
+        for mode in ("fp32", "bf16x6", "bf16x6p", "wide", "latency"):
+            assert K(geom, mode) == netgen.kernels(_net(geom), 70, mode), (geom, mode)
+    for geom in ("A", "C", "D", "H"):
+        assert K(geom, "bf16x6p") == netgen.kernels(_net(geom), 70, "bf16x6p"), geom
