@@ -23,7 +23,10 @@ struct QP {
 // quotients from IEEE division over 68.7e9 random pairs on the GPU
 // (tools/probes/qdiv_probe.hip, denormal scales included), the int8 and
 // parity tests bit-exact with it, the C5 checksum unchanged, C5 +1.2 %
-// (profiles/r05z21_i8_qdiv.txt).  -DCATEARS_I8_QDIV=0 builds the division.
+// (profiles/r05z21_i8_qdiv.txt).  Random pairs never sit on a rounding tie of
+// a tiny scale, where the product does differ: qbyte_rscale's threshold and
+// tests/test_gpu_quant_ties.py cover that.  -DCATEARS_I8_QDIV=0 builds the
+// division.
 #ifndef CATEARS_I8_QDIV
 #define CATEARS_I8_QDIV 1
 #endif
@@ -32,8 +35,10 @@ struct QP {
 // CATEARS_I8_QDIV=1: x / scale as q0 = x * r, r = 1 / scale (correctly
 // rounded), corrected once, q = fma(fma(-scale, q0, x), r, q0) (Markstein's
 // correction: the correctly rounded quotient when r is the correctly rounded
-// reciprocal and nothing overflows); rscale == 0 (1 / scale not finite: a
-// denormal scale) and non-finite results fall back to the division.
+// reciprocal, nothing overflows and the remainder x - scale * q0 does not
+// underflow: it must be exact, and below 2^-149 it cannot be); rscale == 0
+// (qbyte_rscale: 1 / scale not finite, or a scale so small that the remainder
+// can underflow) and non-finite results fall back to the division.
 __device__ __forceinline__ int qbyte(float x, float scale, float zp, float rscale = 0.0f) {
 #if CATEARS_I8_QDIV
   float q;
@@ -55,9 +60,29 @@ __device__ __forceinline__ int qbyte(float x, float scale, float zp, float rscal
 }
 
 // qbyte's rscale for a layer's scale: 1 / scale, or 0 (the division) when
-// that is not finite or the build divides.
+// that is not finite, the scale is below kQdivMinScale or the build divides.
+//
+// The threshold.  A wrong last bit of the quotient changes a byte only where
+// q + zp can reach an n + 0.5 tie, so only for |q| >= 0.5; for |q| < 1/8 no
+// error of the size below moves q + zp across one.  With scale in
+// [2^e, 2^(e+1)), ulp(scale) = 2^(e-23), and |q0| >= 2^-3, so ulp(q0) >=
+// 2^-26, the product scale * q0 is a multiple of ulp(scale) * 2^-26 =
+// 2^(e-49) and x, of q0 * scale's size, of a coarser power of two: so is the
+// remainder x - scale * q0, which the inner fma delivers exactly (it has at
+// most 24 significant bits) as long as that unit is a float: 2^(e-49) >=
+// 2^-149, e >= -100.  (For |q| >= 0.5 alone the unit is ulp(scale) * 2^-24
+// and e >= -102 would do; the two binades are the margin that keeps the
+// neighbours of the lowest tie, q = 0.5 at zp = 0, exact as well.)  Below
+// 2^-100 the remainder is rounded to a multiple of 2^-149 and the corrected
+// quotient can be off by one ulp, which moves bytes on ties: 10 of 1785 tie
+// inputs of the range [0, 7.6e-37] in an exact emulation
+// (tests/quantties.py, which also finds none at or above the threshold over
+// its range list).  This holds with fp32 denormals kept, as these kernels
+// are built; no model has such a scale, and the test is one compare per
+// launch.
+constexpr float kQdivMinScale = 0x1p-100f;
 __device__ __forceinline__ float qbyte_rscale(float scale) {
-  float rs = CATEARS_I8_QDIV ? 1.0f / scale : 0.0f;
+  float rs = (CATEARS_I8_QDIV && scale >= kQdivMinScale) ? 1.0f / scale : 0.0f;
   if (__builtin_isinf(rs) || __builtin_isnan(rs)) rs = 0.0f;
   return rs;
 }

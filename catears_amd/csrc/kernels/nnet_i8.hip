@@ -224,8 +224,8 @@ template <int RPW>
 __device__ __forceinline__ void quantize_rows_fast(const float *__restrict__ x, int ldx, int rows, int width,
                                                    float scale, float zp, int8_t *__restrict__ q, int ldq,
                                                    int32_t *__restrict__ rowsum, int r0, int lane) {
-  float rs = 1.0f / scale;
-  const bool rs_ok = !(__builtin_isinf(rs) || __builtin_isnan(rs));
+  const float rs = qbyte_rscale(scale);
+  const bool rs_ok = rs != 0.0f;  // 0: the division for every element, as qbyte
   int32_t rsum[RPW];
 #pragma unroll
   for (int i = 0; i < RPW; ++i) rsum[i] = 0;

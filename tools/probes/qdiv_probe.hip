@@ -4,6 +4,14 @@
 // x / s when r or q is not finite.  Counts differing quotients over random
 // fp32 pairs: x over [-2^20, 2^20] with random exponents, s over scales the
 // quantize sees (2^-40 .. 2^10, denormal ones included).
+// Random pairs cannot reach the window where the product is wrong: scales
+// between 2.94e-39 and about 2e-37 (normal or nearly so, 1 / s still finite)
+// with x on an n + 0.5 tie of the quantizer, where the remainder x - s * q0
+// falls below 2^-149.  No x drawn here is below 2^-40, so beside a scale
+// that small (the denormal ones) the quotient is beyond 2^80, nowhere near a
+// byte, and the remainder far above 2^-149: exact.  tests/quantties.py
+// constructs the window; qbyte_rscale's threshold (i8_ops.h) sends it to
+// the division.
 //   hipcc --offload-arch=gfx950 -O3 tools/probes/qdiv_probe.hip -o tools/probes/qdp
 #include <hip/hip_runtime.h>
 
