@@ -210,6 +210,39 @@ static int default_gemm() {
   return g >= CE_GPU_GEMM_FP32 && g <= CE_GPU_GEMM_BF16 ? g : -1;
 }
 
+// Every image of one Linear's weights from its n x kpad fp32 matrix (g->n and
+// g->kpad set): wt, the bf16x6 planes, the fragment image, the f16x3 planes
+// with their shift.  *f16_ok: the f16x3 image exists (finite weights).
+static int upload_weight_images(const std::vector<float> &wt, GemmLayer *g, bool *f16_ok) {
+  CE_TRY(g->wt.upload(wt.data(), wt.size() * 4));
+  CE_TRY(upload_split(wt, g->n, g->kpad, &g->wsplit));
+  if (g->kpad % 32 == 0) CE_TRY(upload_wdir(wt, g->n, g->kpad, &g->wdir));
+  return upload_f16(wt, g->n, g->kpad, &g->wf16, &g->w_shift, f16_ok);
+}
+
+// The program-shape rule of the plane modes and the mode a model loads in.
+// bf16x6 program: every step a Linear with its ReLU / BatchNorm fused, a
+// K-tile of 32 inside one splice segment after the first layer (whose
+// spliced block is written padded), output widths multiples of 4.
+// m->x3_ok on entry: every weight matrix has its f16x3 image.
+static int settle_gemm_mode(ce_gpu_model *m) {
+  m->x6_ok = true;
+  for (size_t i = 0; i < m->steps.size(); ++i) {
+    const Step &st = m->steps[i];
+    if (!st.is_gemm || st.gemm.n % 4 != 0 || (i > 0 && st.gemm.din % 32 != 0) || st.gemm.kpad % 32 != 0)
+      m->x6_ok = false;
+  }
+  m->x3_ok = m->x3_ok && m->x6_ok;
+  const int want = default_gemm();
+  if (want < 0) return fail(CE_GPU_EINVAL, "default GEMM mode: not one of 0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p, 4 bf16");
+  m->gemm = want == CE_GPU_GEMM_F16X3 && m->x3_ok   ? CE_GPU_GEMM_F16X3
+            : want == CE_GPU_GEMM_BF16X6_PLANES && m->x6_ok ? CE_GPU_GEMM_BF16X6_PLANES
+            : want == CE_GPU_GEMM_BF16 && m->x6_ok ? CE_GPU_GEMM_BF16
+            : want != CE_GPU_GEMM_FP32 && m->x6_ok ? CE_GPU_GEMM_BF16X6
+                                                    : CE_GPU_GEMM_FP32;
+  return CE_GPU_OK;
+}
+
 static int build_program(const std::vector<RawLayer> &layers, int left, int right, ce_gpu_model *m) {
   m->x3_ok = true;           // cleared by a weight matrix the f16 planes cannot hold
   std::vector<int> pending;  // splice offsets waiting for their Linear
@@ -259,14 +292,13 @@ static int build_program(const std::vector<RawLayer> &layers, int left, int righ
         g.k = in;
         g.kpad = (in + gemm_k_align() - 1) / gemm_k_align() * gemm_k_align();
         g.n = out;
+        g.din_true = g.din;
+        g.n_true = out;
         std::vector<float> wt((size_t)out * g.kpad, 0.0f);  // transpose to n x kpad
         for (int k = 0; k < in; ++k)
           for (int j = 0; j < out; ++j) wt[(size_t)j * g.kpad + k] = L.w[(size_t)k * out + j];
-        CE_TRY(g.wt.upload(wt.data(), wt.size() * 4));
-        CE_TRY(upload_split(wt, out, g.kpad, &g.wsplit));
-        if (g.kpad % 32 == 0) CE_TRY(upload_wdir(wt, out, g.kpad, &g.wdir));
         bool f16_ok = false;
-        CE_TRY(upload_f16(wt, out, g.kpad, &g.wf16, &g.w_shift, &f16_ok));
+        CE_TRY(upload_weight_images(wt, &g, &f16_ok));
         if (!f16_ok) m->x3_ok = false;
         CE_TRY(g.bias.upload(L.b.data(), L.b.size() * 4));
         m->num_params += (int64_t)in * out + out;
@@ -337,24 +369,7 @@ static int build_program(const std::vector<RawLayer> &layers, int left, int righ
     return fail(CE_GPU_ECORRUPT, fmt("Corruption: config context (%d, %d) differs from the nnet's (%d, %d)",
                                      left, right, sum_l, sum_r));
   m->num_pdfs = width;
-  // bf16x6 program: every step a Linear with its ReLU / BatchNorm fused, a
-  // K-tile of 32 inside one splice segment after the first layer (whose
-  // spliced block is written padded), output widths multiples of 4
-  m->x6_ok = true;
-  for (size_t i = 0; i < m->steps.size(); ++i) {
-    const Step &st = m->steps[i];
-    if (!st.is_gemm || st.gemm.n % 4 != 0 || (i > 0 && st.gemm.din % 32 != 0) || st.gemm.kpad % 32 != 0)
-      m->x6_ok = false;
-  }
-  m->x3_ok = m->x3_ok && m->x6_ok;
-  const int want = default_gemm();
-  if (want < 0) return fail(CE_GPU_EINVAL, "default GEMM mode: not one of 0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p, 4 bf16");
-  m->gemm = want == CE_GPU_GEMM_F16X3 && m->x3_ok   ? CE_GPU_GEMM_F16X3
-            : want == CE_GPU_GEMM_BF16X6_PLANES && m->x6_ok ? CE_GPU_GEMM_BF16X6_PLANES
-            : want == CE_GPU_GEMM_BF16 && m->x6_ok ? CE_GPU_GEMM_BF16
-            : want != CE_GPU_GEMM_FP32 && m->x6_ok ? CE_GPU_GEMM_BF16X6
-                                                    : CE_GPU_GEMM_FP32;
-  return CE_GPU_OK;
+  return settle_gemm_mode(m);
 }
 
 // Quantize (src/matrix.cc:329-387) of one weight matrix on the host at load
@@ -729,10 +744,17 @@ int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_mo
   // gpu_gemm: the GEMM mode from the config; a bad name fails before any upload
   int gemm = -1;
   CE_TRY(read_gpu_gemm(cf, &gemm));
+  // gpu_pad_widths: the re-layout onto padded widths, before gpu_gemm
+  int pad = 0;
+  CE_TRY(read_gpu_pad_widths(cf, &pad));
   ce_gpu_model *m = nullptr;
   CE_TRY(load_model(ctx, nnet, prior, left, right, tid2pdf, &m));
   m->chunk = chunk;
   std::unique_ptr<ce_gpu_model> own(m);
+  if (pad) {
+    const int rc = ce_gpu_model_pad_widths(ctx, m);
+    if (rc != CE_GPU_OK) return fail(rc, cf.file + ": gpu_pad_widths = 1: " + last_error());
+  }
   if (gemm >= 0) {
     const int rc = ce_gpu_model_set_gemm(m, gemm);
     if (rc != CE_GPU_OK) return fail(rc, cf.file + ": gpu_gemm = " + cf.kv["gpu_gemm"] + ": " + last_error());
@@ -1253,8 +1275,90 @@ int ce_gpu_sum_f64_many(void *stream, int count, const float *const *d_x, const 
   return launch_sum_f64(reinterpret_cast<hipStream_t>(stream), count, d_x, n, d_part, d_acc);
 }
 
+static int download(const DevBuf &b, int n, float fill, int npad, std::vector<float> *out) {
+  out->assign(npad, fill);
+  if (n) CE_HIP(hipMemcpy(out->data(), b.ptr, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return CE_GPU_OK;
+}
+
+int ce_gpu_model_pad_widths(ce_gpu_ctx *ctx, ce_gpu_model *m) {
+  if (!ctx || !m) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->int8) return fail(CE_GPU_EINVAL, "model_pad_widths: the model is quantized");
+  if (m->x6_ok) return CE_GPU_OK;  // already inside the plane modes' envelope (or padded)
+  for (const Step &st : m->steps)
+    if (!st.is_gemm) return fail(CE_GPU_ENOTSUP, "model_pad_widths: the program has an unfused row op");
+  CE_HIP(hipSetDevice(ctx->device));
+  CE_HIP(hipStreamSynchronize(ctx->stream));
+  // the new layers are built beside the old ones: a failure leaves the model as it was
+  const size_t nl = m->steps.size();
+  std::vector<GemmLayer> pad(nl);
+  bool f16_all = true;
+  int prev_n = 0, max_width = 0;
+  for (size_t i = 0; i < nl; ++i) {
+    const GemmLayer &g = m->steps[i].gemm;
+    GemmLayer &p = pad[i];
+    const int round = i + 1 == nl ? 4 : 32;
+    p.n = (g.n + round - 1) / round * round;
+    p.din = i == 0 ? g.din : prev_n;
+    p.din_true = g.din;
+    p.n_true = g.n;
+    p.nseg = g.nseg;
+    for (int s = 0; s < 8; ++s) p.off[s] = g.off[s];
+    p.k = p.nseg * p.din;
+    p.kpad = (p.k + gemm_k_align() - 1) / gemm_k_align() * gemm_k_align();
+    for (int q = 0; q < 4; ++q) p.post[q] = g.post[q];
+    p.npost = g.npost;
+    p.in_left = g.in_left;
+    p.in_right = g.in_right;
+    // segment s's true columns at s * din_pad, zero columns behind them;
+    // zero rows for the padded units
+    std::vector<float> old((size_t)g.n * g.kpad), wt((size_t)p.n * p.kpad, 0.0f);
+    CE_HIP(hipMemcpy(old.data(), g.wt.ptr, old.size() * 4, hipMemcpyDeviceToHost));
+    for (int j = 0; j < g.n; ++j)
+      for (int s = 0; s < g.nseg; ++s)
+        memcpy(&wt[(size_t)j * p.kpad + (size_t)s * p.din], &old[(size_t)j * g.kpad + (size_t)s * g.din],
+               (size_t)g.din * 4);
+    bool f16_ok = false;
+    CE_TRY(upload_weight_images(wt, &p, &f16_ok));
+    f16_all = f16_all && f16_ok;
+    // a padded unit: bias 0, BatchNorm scale 1 and offset 0 -- +0 after any post chain
+    std::vector<float> v;
+    CE_TRY(download(g.bias, g.n, 0.0f, p.n, &v));
+    CE_TRY(p.bias.upload(v.data(), v.size() * 4));
+    if (g.bn_scale.ptr) {
+      CE_TRY(download(g.bn_scale, g.n, 1.0f, p.n, &v));
+      CE_TRY(p.bn_scale.upload(v.data(), v.size() * 4));
+      CE_TRY(download(g.bn_offset, g.n, 0.0f, p.n, &v));
+      CE_TRY(p.bn_offset.upload(v.data(), v.size() * 4));
+    }
+    prev_n = p.n;
+    max_width = std::max(max_width, p.n);
+  }
+  for (size_t i = 0; i < nl; ++i) m->steps[i].gemm = std::move(pad[i]);
+  m->max_width = max_width;
+  m->padded = true;
+  m->x3_ok = f16_all;
+  return settle_gemm_mode(m);
+}
+
+int ce_gpu_model_padded_widths(const ce_gpu_model *m, int *h_true, int *h_padded, int capacity, int *count) {
+  if (!m || !count) return fail(CE_GPU_EINVAL, "NULL argument");
+  int n = 0;
+  for (const Step &st : m->steps) {
+    if (!st.is_gemm) continue;
+    if (n < capacity) {
+      if (h_true) h_true[n] = st.gemm.n_true;
+      if (h_padded) h_padded[n] = st.gemm.n;
+    }
+    ++n;
+  }
+  *count = n;
+  return CE_GPU_OK;
+}
+
 int ce_gpu_model_quantize(ce_gpu_ctx *ctx, ce_gpu_model *m) {
   if (!ctx || !m) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->padded) return fail(CE_GPU_EINVAL, "model_quantize: the model is on padded widths (ce_gpu_model_pad_widths)");
   if (m->int8_static) return fail(CE_GPU_EINVAL, "model_quantize: the model is static int8");
   if (m->int8) return CE_GPU_OK;
   CE_HIP(hipSetDevice(ctx->device));
@@ -1315,6 +1419,8 @@ int ce_gpu_model_calibrate(ce_gpu_ctx *ctx, const ce_gpu_model *m, const ce_gpu_
 
 int ce_gpu_model_quantize_static(ce_gpu_ctx *ctx, ce_gpu_model *m, const float *h_ranges, int n_ranges) {
   if (!ctx || !m || !h_ranges) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->padded)
+    return fail(CE_GPU_EINVAL, "model_quantize_static: the model is on padded widths (ce_gpu_model_pad_widths)");
   if (m->int8) return fail(CE_GPU_EINVAL, "model_quantize_static: the model is already quantized");
   if (n_ranges != m->num_linear)
     return fail(CE_GPU_EINVAL, fmt("model_quantize_static: %d ranges for %d Linear layers", n_ranges, m->num_linear));

@@ -226,6 +226,10 @@ struct GemmLayer {
   int nseg = 1;           // splice indices (segments of the K dimension)
   int off[8] = {0};       // row offset of each segment
   int k = 0, kpad = 0, n = 0;
+  // the net's own widths: what din and n were before ce_gpu_model_pad_widths
+  // moved the layer onto padded ones (equal to them otherwise).  Columns
+  // din_true .. din - 1 of every segment and units n_true .. n - 1 are zero.
+  int din_true = 0, n_true = 0;
   DevBuf wt;              // n x kpad, K-contiguous (transposed MAT0)
   DevBuf wsplit;          // n x 3*kpad bf16: wt as three planes (bf16x6 GEMM)
   DevBuf wf16;            // n x 2*kpad fp16: wt * 2^w_shift as two planes (f16x3 GEMM)
@@ -410,6 +414,7 @@ struct ce_gpu_model {
   int gemm = 0;                      // CE_GPU_GEMM_* for the fp32 program
   bool x6_ok = false;                // program shape the bf16x6 / f16x3 paths take
   bool x3_ok = false;                // ... and every weight fits the f16x3 planes
+  bool padded = false;               // ce_gpu_model_pad_widths re-laid the layers (GemmLayer::n_true)
   std::vector<catears::Step> steps;  // all but the final log-softmax
   catears::DevBuf log_prior;         // num_pdfs
   std::vector<int32_t> tid2pdf;

@@ -224,6 +224,19 @@ int read_gpu_gemm(const Config &cf, int *mode) {
   return CE_GPU_OK;
 }
 
+int read_gpu_pad_widths(const Config &cf, int *pad) {
+  *pad = 0;
+  auto it = cf.kv.find("gpu_pad_widths");
+  if (it == cf.kv.end()) return CE_GPU_OK;
+  if (it->second != "0" && it->second != "1")
+    return fail(CE_GPU_EINVAL, cf.file + ": gpu_pad_widths = " + it->second + ": not 0 or 1");
+  *pad = it->second == "1";
+  if (*pad && cf.kv.count("gpu_int8_ranges"))
+    return fail(CE_GPU_EINVAL,
+                cf.file + ": gpu_pad_widths = 1 beside gpu_int8_ranges: a padded model takes no int8 form");
+  return CE_GPU_OK;
+}
+
 // ------------------------------------------------------------------ NN02 --
 
 int read_nnet(Reader &rd, std::vector<RawLayer> *layers, int *hl, int *hr) {

@@ -89,6 +89,13 @@ bool gemm_mode_from_name(const char *name, int *mode);
 // and value in the message.
 int read_gpu_gemm(const Config &cf, int *mode);
 
+// The configuration key gpu_pad_widths = 0 | 1 (this implementation's own):
+// 1 re-lays the loaded model with ce_gpu_model_pad_widths before gpu_gemm is
+// applied.  Key absent: *pad = 0, OK.  Any other value fails with
+// CE_GPU_EINVAL and the key and value in the message; so does the value 1
+// beside gpu_int8_ranges (a padded model takes no int8 form), naming both keys.
+int read_gpu_pad_widths(const Config &cf, int *pad);
+
 // Layer ids (src/nnet.h:21-30).
 enum LayerId { kLinear = 0, kReLU = 1, kNormalize = 2, kSoftmax = 3, kSplice = 6, kBatchNorm = 7,
                kLogSoftmax = 8, kNarrow = 9 };

@@ -146,8 +146,9 @@ static bool lat_fused_final() {
 static int tap_input(ce_gpu_ctx *ctx, CalibTap *tap, const GemmLayer &g, const float *x, int ldx, int rows,
                      const int *row_map) {
   if (!tap) return CE_GPU_OK;
-  return launch_i8_range(ctx->stream, x, ldx, rows, g.din, row_map, tap->row_edge, g.in_left, g.in_right, tap->part,
-                         tap->ranges + 2 * tap->linear++);
+  // the net's own columns: a padded model's zero columns are no activations
+  return launch_i8_range(ctx->stream, x, ldx, rows, g.din_true, row_map, tap->row_edge, g.in_left, g.in_right,
+                         tap->part, tap->ranges + 2 * tap->linear++);
 }
 
 // An incremental session chunk (inc, internal.h) runs every Linear causally:
@@ -292,7 +293,7 @@ static Layout layout_x6f(const ce_gpu_model *m, int rows, bool latency, bool pla
   Layout L;
   L.blk = round_up((size_t)rows * max_operand_width(m, 32) * (planes ? 3 : 2) / 2, 64);
   L.out = 2 * L.blk;
-  L.ws_floats = L.out + (size_t)rows * m->num_pdfs;
+  L.ws_floats = L.out + (size_t)rows * m->steps.back().gemm.n;  // the last layer's leading dimension
   for (size_t i = 0; latency && i < m->steps.size(); ++i) {
     const GemmLayer &g = m->steps[i].gemm;
     const int kpad = i == 0 ? g.kpad : g.nseg * g.din;
@@ -382,7 +383,10 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
       ProfScope prof(ctx, CE_GPU_PROF_GEMM);
       if (ctx->latency) {
         const size_t pf = x6_lat_part_floats(a.m, a.n, x6_lat_slices(a.kpad, a.n));
-        if (last && lat_fused_final()) a.tail = tail;  // the reduce may run inside the finalize
+        // the reduce may run inside the finalize -- which writes whole
+        // float4 chunks of a row as wide as the partials, so not for a last
+        // layer on a padded width (lat_reduce + launch_finalize then)
+        if (last && lat_fused_final() && g.n == m->num_pdfs) a.tail = tail;
         CE_TRY(launch_gemm_bf16x6_lat(ctx->stream, a, ctx->lat_part.as<float>(), pf, ctx->lat_tickets.as<unsigned>()));
       } else if (!(diag_skip() & (i == 0 ? 1 : last ? 16 : 32))) {
         CE_TRY(launch_gemm_bf16x6(ctx->stream, a));
@@ -471,7 +475,7 @@ static Layout layout_chain16(const ce_gpu_model *m, int rows) {
   Layout L;
   L.blk = round_up(((size_t)rows * Mode::kWords * max_operand_width(m, Mode::kRound) + 1) / 2, 64);
   L.out = 2 * L.blk;
-  L.ws_floats = L.out + (size_t)rows * m->num_pdfs;
+  L.ws_floats = L.out + (size_t)rows * m->steps.back().gemm.n;  // the last layer's leading dimension
   L.overflow = Mode::kOverflow;
   return L;
 }

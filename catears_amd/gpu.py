@@ -40,6 +40,7 @@ ABI = [
     "ce_gpu_i8_latency_plan", "ce_gpu_debug_i8_latency_launches",
     "ce_gpu_gemm_mode_from_name",
     "ce_gpu_sessions_create_ex", "ce_gpu_sessions_stats",
+    "ce_gpu_model_pad_widths", "ce_gpu_model_padded_widths",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -132,6 +133,8 @@ def lib():
         "ce_gpu_model_quant_params": (ci, [vp, vp, vp, ci, pi]),
         "ce_gpu_i8_latency_plan": (ci, [ci, ci, ci, pi, pi]),
         "ce_gpu_debug_i8_latency_launches": (ci, [pi64]),
+        "ce_gpu_model_pad_widths": (ci, [vp, vp]),
+        "ce_gpu_model_padded_widths": (ci, [vp, vp, vp, ci, pi]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -314,6 +317,26 @@ class Model:
         check(lib().ce_gpu_model_quant_params(self.h, s.ctypes.data_as(ctypes.c_void_p),
                                               z.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
         return s, z
+
+    def pad_widths(self, ctx):
+        """Re-lay the model onto padded layer widths (hidden widths to
+        multiples of 32, the last to a multiple of 4, zero weights in the
+        pads) so that every GEMM mode, latency mode and wide tiles take a net
+        of any width; the model then is in the mode it would have loaded in.
+        Nothing changes for a model already inside the envelope
+        (ce_gpu_model_pad_widths)."""
+        check(lib().ce_gpu_model_pad_widths(ctx.h, self.h))
+        return self
+
+    def padded_widths(self):
+        """(true int32[n], padded int32[n]): each Linear's output width as the
+        net has it and as the model runs it (ce_gpu_model_padded_widths)."""
+        n = ctypes.c_int()
+        check(lib().ce_gpu_model_padded_widths(self.h, None, None, 0, ctypes.byref(n)))
+        t, p = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        check(lib().ce_gpu_model_padded_widths(self.h, t.ctypes.data_as(ctypes.c_void_p),
+                                               p.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return t, p
 
     def set_gemm(self, mode):
         """Matrix-core form of the fp32 Linear layers: "fp32" (fp32 MFMA),

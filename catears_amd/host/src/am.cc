@@ -95,6 +95,28 @@ Status AcousticModel::Read(const Configuration &conf) {
   if (rc != CE_GPU_OK) return Status::Corruption(util::Format("{}: {}", nnet_file, ce_gpu_last_error()));
   int pdfs = 0;
   ce_gpu_model_info(model_, nullptr, nullptr, &feat_dim_, &pdfs, nullptr, nullptr);
+  // gpu_pad_widths = 1: the model re-laid onto padded layer widths
+  // (ce_gpu_model_pad_widths), before gpu_gemm, so that every GEMM mode and
+  // latency mode take a net of any width.  Not beside gpu_int8_ranges: a
+  // padded model takes no int8 form.
+  const std::string pad = conf.GetStringOrElse("gpu_pad_widths", "0");
+  if (pad != "0" && pad != "1") {
+    ce_gpu_model_destroy(model_);
+    model_ = nullptr;
+    return Status::Corruption(util::Format("gpu_pad_widths = {}: not 0 or 1", pad));
+  }
+  if (pad == "1") {
+    const bool with_int8 = !conf.GetPathOrElse("gpu_int8_ranges", "").empty();
+    const int rcp = with_int8 ? CE_GPU_EINVAL : ce_gpu_model_pad_widths(rt.ctx(), model_);
+    if (rcp != CE_GPU_OK) {
+      const std::string why =
+          with_int8 ? std::string("gpu_pad_widths = 1 beside gpu_int8_ranges: a padded model takes no int8 form")
+                    : util::Format("gpu_pad_widths = 1: {}", ce_gpu_last_error());
+      ce_gpu_model_destroy(model_);
+      model_ = nullptr;
+      return rcp == CE_GPU_ENOTSUP ? Status::NotImplemented(why) : Status::Corruption(why);
+    }
+  }
   // gpu_gemm = <name>: the model's GEMM mode (ce_gpu_gemm_mode_from_name's
   // names; "bf16" is the plain bf16 mode).  Beside gpu_int8_ranges it is
   // accepted and has no effect: the int8 form wins.

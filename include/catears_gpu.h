@@ -80,7 +80,9 @@ const char *ce_gpu_last_error(void);
  * the config key gpu_int8_ranges) only adds to 0.7, and so does the plain
  * bf16 GEMM mode (CE_GPU_GEMM_BF16, ce_gpu_gemm_mode_from_name, the config
  * key gpu_gemm), and so do the incremental session sets
- * (ce_gpu_sessions_create_ex, ce_gpu_sessions_stats). */
+ * (ce_gpu_sessions_create_ex, ce_gpu_sessions_stats), and so does the
+ * re-layout onto padded widths (ce_gpu_model_pad_widths,
+ * ce_gpu_model_padded_widths, the config key gpu_pad_widths). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -242,6 +244,11 @@ int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
  * CE_GPU_EINVAL and the key and value in the text, a mode the model does not
  * allow with CE_GPU_ENOTSUP.  Beside gpu_int8_ranges it is accepted and has
  * no effect (the int8 form wins).
+ * A third: gpu_pad_widths = 1 re-lays the loaded model with
+ * ce_gpu_model_pad_widths before gpu_gemm is applied, so gpu_gemm = bf16
+ * works on a model of any width; a value other than 0 or 1, or the value 1
+ * beside gpu_int8_ranges, fails with CE_GPU_EINVAL and the key(s) in the
+ * text before anything is uploaded.
  * Fails with CE_GPU_ENOTSUP for a topology whose whole-utterance result
  * would differ from the reference's chunked one. */
 int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_model **out);
@@ -389,6 +396,50 @@ int ce_gpu_model_get_gemm(const ce_gpu_model *m, int *mode);
  * (CE_GPU_GEMM_BF16X6_PLANES), "f16x3", "bf16".  Any other name, or a NULL
  * argument: CE_GPU_EINVAL.  Needs no device. */
 int ce_gpu_gemm_mode_from_name(const char *name, int *mode);
+
+/* Re-lays a loaded model onto padded layer widths, so that a net of any
+ * width can run the matrix-core modes above (and with them latency mode, wide
+ * tiles and sessions in bf16x6 / bf16).  Opt-in: a model outside the
+ * envelope of CE_GPU_GEMM_BF16X6 still loads as CE_GPU_GEMM_FP32.
+ *   Every hidden Linear's output width goes up to the next multiple of 32,
+ * the last Linear's to the next multiple of 4; a later Linear's input width
+ * is the previous padded width, splice segment s holding its true columns at
+ * s * padded_width with zero weight columns behind them.  A padded unit has
+ * zero weights, a zero bias and, under a fused BatchNorm, scale 1 and
+ * offset 0: its activation is +0 after any post chain, in every mode, and it
+ * meets only zero weights in the next layer.  Every weight image is rebuilt,
+ * the load-time rule is applied again, and the model ends in the mode it
+ * would have loaded in (CE_GPU_GEMM_BF16X6 in the product library).
+ *   Definition of the modes on a padded model: a mode's definition applies
+ * to the padded program.  A pad contributes products that are exactly zero,
+ * so each mode computes the original net under its own definition, with a K
+ * order that has zeros inserted at the segment ends: for the fp32-class
+ * modes again an fp32 GEMM in another summation order; for CE_GPU_GEMM_BF16
+ * every invariance listed above holds unchanged; on exact-integer nets every
+ * mode gives the original net's bits.  (Non-finite activations are outside
+ * this: 0 * inf is NaN.)
+ *   The model keeps the net's own widths: ce_gpu_model_info reports the same
+ * input_dim, num_pdfs and num_params as before, no entry point reads or
+ * writes a pad column of a caller's buffer, LogSoftmax and the prior run over
+ * num_pdfs columns, and ce_gpu_model_calibrate folds the true columns only.
+ * In latency mode the last layer's slice reduce is its own launch when that
+ * layer was padded (the fused finalize needs num_pdfs % 4 == 0); same bits.
+ *   Returns CE_GPU_OK and changes nothing for a model already inside the
+ * envelope; CE_GPU_ENOTSUP, nothing changed, for a program with an unfused row
+ * op; CE_GPU_EINVAL for an int8 model of either form.  On a padded model
+ * ce_gpu_model_quantize and ce_gpu_model_quantize_static return
+ * CE_GPU_EINVAL (the int8 programs take any width on the unpadded model, and
+ * a zero pad column is not neutral under an unclamped zero point).
+ * Irreversible for this model handle.  Host-synchronous; allocates.  Like
+ * the quantize entries it belongs right after the load: a session set sizes
+ * its caches from the model's widths when it is created. */
+int ce_gpu_model_pad_widths(ce_gpu_ctx *ctx, ce_gpu_model *m);
+
+/* Each Linear's output width as the net has it (h_true) and as the model
+ * runs it (h_padded; equal unless ce_gpu_model_pad_widths changed it), for
+ * logging and tests: copies min(capacity, *count) of each, *count = the
+ * number of Linear layers.  Either array may be NULL. */
+int ce_gpu_model_padded_widths(const ce_gpu_model *m, int *h_true, int *h_padded, int capacity, int *count);
 
 /* tid2pdf map (AcousticModel::TransitionPdfIdMap, src/am.h:38-40).  Copies
  * min(capacity, size) ints to h_out and returns the size via *size. */
