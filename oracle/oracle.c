@@ -13,13 +13,15 @@
  * -ffp-contract=off (see oracle/Makefile): the reference is built for x86-64
  * without FMA, so no multiply-add is ever contracted there.
  *
- * Pinning: srfft is checked bit-for-bit against the reference's own srfft.cc
- * compiled from /root/reference (oracle/_ref), fbank / CMVN against the Kaldi
- * dumps the reference's tests hold (test/data/*.txt), nnet layers against the
- * known answers of test/nnet_test.cc, the int8 GEMM bit-for-bit against the
- * vendored gemmlowp compiled from /root/reference (oracle/_ref).  The fp32
- * GEMM inside LinearLayer is OpenBLAS in the reference (not vendored); here it
- * is the k-sequential fp32 sum of SimpleMatMat (src/matrix.cc:275-292).
+ * Pinning: srfft, fbank, CMVN, Quantize, the int8 GEMM, every nnet layer and
+ * the AcousticModel's streaming are checked bit-for-bit against the
+ * reference's own sources compiled into oracle/_ref (oracle/ref_harness.cc,
+ * tests/test_oracle_vs_reference.py); fbank / CMVN also against the Kaldi
+ * dumps the reference's tests hold (the .txt files of test/data), nnet layers against the
+ * known answers of test/nnet_test.cc.  The fp32 GEMM inside LinearLayer is
+ * OpenBLAS in the reference (not vendored, its order not pinned); here it is
+ * the k-sequential fp32 sum of SimpleMatMat (src/matrix.cc:275-292), compared
+ * with the reference on exact-integer operands.
  */
 #include <float.h>
 #include <math.h>

@@ -63,22 +63,123 @@ def lib():
     return _LIB
 
 
-def ref_lib():
-    """oracle/_ref/libref.so (reference srfft.cc + gemmlowp), or None."""
+def ref_lib(hot_path=False):
+    """oracle/_ref/libref.so (the reference's own code behind
+    oracle/ref_harness.cc), or None when it is not built.  Every build has the
+    SRFFT and gemmlowp entries.  hot_path=True: the library must also hold the
+    reference's front end, Quantize, u8 GEMM, nnet and acoustic model (ref_cmvn
+    ... ref_am); None for a library from before those entries that could not
+    be rebuilt (oracle/Makefile rebuilds it wherever the reference tree is)."""
     global _REF
+    if _REF is not None and hot_path and not _REF.has_hot_path:
+        return None
     if _REF is None:
         path = os.path.join(HERE, "_ref", "libref.so")
         if not os.path.exists(path):
             return None
         R = ctypes.CDLL(path)
+        ci, cl, cf, i32 = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_int32
+        pi = ctypes.POINTER(ci)
         R.ref_srfft_new.restype = ctypes.c_void_p
-        R.ref_srfft_new.argtypes = [ctypes.c_int]
+        R.ref_srfft_new.argtypes = [ci]
         R.ref_srfft_free.argtypes = [ctypes.c_void_p]
-        R.ref_srfft_forward.argtypes = [ctypes.c_void_p, f32p, ctypes.c_int, f32p]
-        R.ref_gemm_u8u8f32.argtypes = [ctypes.c_int] * 3 + [u8p, ctypes.c_float, ctypes.c_int32,
-                                                             u8p, ctypes.c_float, ctypes.c_int32, f32p]
+        R.ref_srfft_forward.argtypes = [ctypes.c_void_p, f32p, ci, f32p]
+        u8gemm = [ci] * 3 + [u8p, cf, i32, u8p, cf, i32, f32p]
+        R.ref_gemm_u8u8f32.argtypes = u8gemm
+        R.has_hot_path = all(hasattr(R, name) for name in (
+            "ref_matmat_u8u8f32", "ref_cmvn", "ref_fbank", "ref_fbank_stream", "ref_quantize",
+            "ref_nnet_propagate", "ref_am"))
+        if R.has_hot_path:
+            R.ref_matmat_u8u8f32.argtypes = u8gemm
+            R.ref_cmvn.argtypes = [f32p, f32p, ci, f32p]
+            R.ref_fbank.restype = ci
+            R.ref_fbank.argtypes = [f32p, cl, f32p, ci]
+            R.ref_fbank_stream.restype = ci
+            R.ref_fbank_stream.argtypes = [f32p, cl, i32p, ci, f32p, ci]
+            R.ref_quantize.argtypes = [f32p, ci, ci, u8p, ctypes.POINTER(cf), ctypes.POINTER(i32)]
+            R.ref_nnet_propagate.restype = ci
+            R.ref_nnet_propagate.argtypes = [ctypes.c_char_p, f32p, ci, ci, f32p, cl, pi, pi, i32p]
+            R.ref_am.restype = ci
+            R.ref_am.argtypes = [ctypes.c_char_p, f32p, ci, f32p, cl, pi, i32p, ci, pi]
         _REF = R
-    return _REF
+    return _REF if _REF.has_hot_path or not hot_path else None
+
+
+# ------------------------------------------- the reference itself (libref) --
+# Thin wrappers over ref_lib(): the reference's own code on numpy arrays, for
+# the tests that pin this oracle to it (tests/test_oracle_vs_reference.py).
+
+def ref_cmvn(global_stats, feats):
+    """CMVN::GetFrame for every frame in order."""
+    feats = np.ascontiguousarray(feats, np.float32).reshape(-1, 40)
+    out = np.zeros_like(feats)
+    ref_lib().ref_cmvn(np.ascontiguousarray(global_stats, np.float32), feats, len(feats), out)
+    return out
+
+
+def ref_fbank(wave, pieces=None):
+    """Fbank::Process: one call, or one Instance fed pieces of the given sizes
+    (cycled) when `pieces` is a list."""
+    wave = np.ascontiguousarray(wave, np.float32)
+    cap = max(len(wave) // 160 + 1, 1)
+    out = np.zeros((cap, 40), np.float32)
+    if pieces is None:
+        t = ref_lib().ref_fbank(wave, len(wave), out, cap)
+    else:
+        p = np.ascontiguousarray(pieces, np.int32)
+        t = ref_lib().ref_fbank_stream(wave, len(wave), p, len(p), out, cap)
+    if t < 0:
+        raise RuntimeError("ref_fbank: more frames than the wave can hold")
+    return out[:t].copy()
+
+
+def ref_quantize(x):
+    """pocketkaldi::Quantize -> (bytes, scale, zero point); x is 1-D or 2-D."""
+    x = np.ascontiguousarray(x, np.float32)
+    m = x.reshape(1, -1) if x.ndim == 1 else x
+    q = np.zeros(m.shape, np.uint8)
+    s, z = ctypes.c_float(), ctypes.c_int32()
+    ref_lib().ref_quantize(m, m.shape[0], m.shape[1], q, ctypes.byref(s), ctypes.byref(z))
+    return q.reshape(x.shape), s.value, z.value
+
+
+def ref_matmat_u8u8f32(a, sa, zpa, b, sb, zpb):
+    """MatMat_U8U8F32 of the reference's matrix.cc."""
+    m, k = a.shape
+    n = b.shape[1]
+    c = np.zeros((m, n), np.float32)
+    ref_lib().ref_matmat_u8u8f32(m, n, k, np.ascontiguousarray(a), sa, zpa, np.ascontiguousarray(b), sb, zpb, c)
+    return c
+
+
+def ref_nnet_propagate(nnet_path, x, max_cols=4096):
+    """Nnet::Read of the file, then Nnet::Propagate -> (y, left, right)."""
+    x = np.ascontiguousarray(x, np.float32)
+    cap = x.shape[0] * max_cols
+    out = np.zeros(cap, np.float32)
+    r, c = ctypes.c_int(), ctypes.c_int()
+    ctxs = np.zeros(2, np.int32)
+    rc = ref_lib().ref_nnet_propagate(os.fsencode(nnet_path), x, x.shape[0], x.shape[1], out, cap,
+                                      ctypes.byref(r), ctypes.byref(c), ctxs)
+    if rc != 0:
+        raise RuntimeError(f"ref_nnet_propagate({nnet_path}): {rc}")
+    return out[:r.value * c.value].reshape(r.value, c.value).copy(), int(ctxs[0]), int(ctxs[1])
+
+
+def ref_am(conf_path, feats, num_pdfs, max_tids=1 << 16):
+    """AcousticModel::Read, Process per frame, EndOfStream -> (rows x pdfs
+    log-likelihoods, num_pdfs as read, tid2pdf as read)."""
+    feats = np.ascontiguousarray(feats, np.float32).reshape(-1, 40)
+    cap = len(feats) + 1
+    out = np.zeros((cap, num_pdfs), np.float32)
+    tid = np.zeros(max_tids, np.int32)
+    npdf, ntid = ctypes.c_int(), ctypes.c_int()
+    rows = ref_lib().ref_am(os.fsencode(conf_path), feats, len(feats), out, out.size, ctypes.byref(npdf),
+                            tid, max_tids, ctypes.byref(ntid))
+    if rows < 0 or ntid.value > max_tids:
+        raise RuntimeError(f"ref_am({conf_path}): {rows}")
+    y = out.reshape(-1)[:rows * npdf.value].reshape(rows, npdf.value).copy()
+    return y, npdf.value, tid[:ntid.value].copy()
 
 
 # ---------------------------------------------------------------- signal --

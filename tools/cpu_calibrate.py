@@ -5,9 +5,10 @@
 committed as profiles/cpu_calibration.json and bench.py quotes it beside its
 cpu_baseline).
 
-The reference's hot path cannot be built here whole (matrix.cc needs
-<cblas.h>).  What can be compared on one core, on the same
-10 s synthetic utterance:
+The reference's hot path builds here only with a BLAS of our own behind
+MatMat (no <cblas.h> is installed: oracle/ref_harness.cc's plain loop,
+DESIGN.md §5), so its nnet cannot be timed.  What can be compared on one core,
+on the same 10 s synthetic utterance:
   * the real FFT: the reference's SRFFT::Compute (src/srfft.cc:370-459,
     compiled by oracle/Makefile into oracle/_ref/libref.so) against the
     oracle's restatement, on the utterance's 998 windowed frames;
