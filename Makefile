@@ -40,7 +40,7 @@ HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc
            $(SRC)/nnet_programs.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
         $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
-HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_programs.h
+HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_programs.h
 
 all: $(LIB) oracle
 
@@ -49,10 +49,12 @@ lib: $(LIB)
 
 # the bf16x6 GEMM's small per-lane arrays stay in registers (hipcc would
 # otherwise promote one into LDS at 1 block/CU: +36 KB of LDS traffic)
-$(OBJ)/gemm_bf16x6.o $(OBJ)/gemm_f16x3.o: HIPFLAGS += -mllvm -disable-promote-alloca-to-lds=1
+$(OBJ)/gemm_bf16x6.o $(OBJ)/gemm_bf16x6_exp.o $(OBJ)/gemm_f16x3.o: HIPFLAGS += -mllvm -disable-promote-alloca-to-lds=1
 # no SLP-packed v_pk_add_f32 beside MFMAs (MI355X_MICROARCH.md: packed f32
 # VALU costs more issue cycles than the scalar pair in an MFMA gap)
-$(OBJ)/gemm_bf16x6.o: HIPFLAGS += -fno-slp-vectorize $(X6FLAGS)
+# gemm_bf16x6_exp.hip: the same kernels' measurement variants (empty in the
+# product build), so the same flags
+$(OBJ)/gemm_bf16x6.o $(OBJ)/gemm_bf16x6_exp.o: HIPFLAGS += -fno-slp-vectorize $(X6FLAGS)
 
 # the exact fbank kernel holds a frame's FFT in 64 registers per lane: the
 # SLP vectorizer's packed f32 pairs cost it ~20 registers of shuffles and

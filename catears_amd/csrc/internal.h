@@ -520,6 +520,11 @@ int launch_gemm_bf16x6_lat(hipStream_t s, const X6Gemm &a, float *part, size_t p
 // the reduce launch followed by launch_finalize.
 int launch_lat_finalize(hipStream_t s, const LatTail &t, int first, int rows, bool log_softmax,
                         const float *log_prior, const int *row_dst, float *out);
+// The splice offsets of up to 8 segments, by value in the kernel arguments of
+// the 16-bit splice_pad kernels (bf16x6 planes, bf16, f16x3).
+struct SpliceIdx8 {
+  int v[8];
+};
 // splice_pad (below) written as three bf16 planes of width po: out row r at
 // out + r * 3 * po.
 int launch_splice_pad_split(hipStream_t s, const float *in, int ld_in, int rows, int din, int nseg, const int *off,

@@ -45,10 +45,15 @@
 #include <hip/hip_runtime.h>
 
 #include "../internal.h"
+#include "../lds_dma.h"
 #include "../tile_order.h"
 
 namespace catears {
 namespace {
+
+using dma::clampi;
+using dma::glds16;
+using dma::wait_vmcnt;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -66,18 +71,6 @@ struct B16Args {
   int npost, post_mode;
   int tiles_m, tiles_n, group;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void glds16(const char *src, char *lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                   (__attribute__((address_space(3))) void *)lds_dst, 16, 0, 0);
-}
 
 // two floats -> two bf16, round to nearest even (v_cvt_pk_bf16_f32), a in the low half
 __device__ __forceinline__ uint32_t bf16_pair(float a, float b) {
@@ -235,10 +228,6 @@ __global__ __launch_bounds__(C::NT) void gemm_bf16_kernel(B16Args p) {
 // First layer: the gathered (row_map), spliced, zero-padded input rows as
 // bf16 (splice_pad_split_kernel's plane 0): out row r is `po` wide, columns
 // nseg*din .. po-1 are zero.
-struct SpliceIdx8 {
-  int v[8];
-};
-
 __global__ __launch_bounds__(256) void splice_pad_bf16_kernel(const float *__restrict__ in, int ld_in, int rows, int din,
                                                               int nseg, SpliceIdx8 idx, const int *__restrict__ row_map,
                                                               uint16_t *__restrict__ out, int po) {

@@ -31,10 +31,16 @@
 #include <string>
 #include <type_traits>
 
+#include "../bf16_split.h"
 #include "../internal.h"
+#include "../lds_dma.h"
 
 namespace catears {
 namespace {
+
+using dma::clampi;
+using split::Planes2;
+using split::split3_pair;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -67,26 +73,6 @@ struct LatArgs {
   int post[4];
   int npost, post_mode;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// v = h + m + l in bf16 for two values (the same conversions as
-// gemm_bf16x6.hip split3_pair: bit-identical planes)
-struct Planes2 {
-  uint32_t h, m, l;
-};
-__device__ __forceinline__ Planes2 split3_pair(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  auto cvt = [](float x, float y) { return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){x, y}, bf16x2)); };
-  auto lo = [](uint32_t u) { return __builtin_bit_cast(float, u << 16); };
-  auto hi = [](uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-  const uint32_t p0 = cvt(a, b);
-  const float ra = a - lo(p0), rb = b - hi(p0);
-  const uint32_t p1 = cvt(ra, rb);
-  const float sa = ra - lo(p1), sb = rb - hi(p1);
-  return Planes2{p0, p1, cvt(sa, sb)};
-}
 
 // MULTI: the block loops over several row tiles (large windows); a single
 // tile is straight-line code (a loop would make the compiler drain the weight

@@ -254,10 +254,6 @@ __global__ __launch_bounds__(C::NT, 1) void gemm_f16x3_kernel(X3Args p) {
 
 // First layer: splice_pad_kernel's block (rows x po, zero padded) written as
 // the two activation planes.  Features beyond the range set the flag too.
-struct SpliceIdx8 {
-  int v[8];
-};
-
 __global__ __launch_bounds__(256) void splice_pad_f16_kernel(const float *__restrict__ in, int ld_in, int rows,
                                                              int din, int nseg, SpliceIdx8 idx,
                                                              const int *__restrict__ row_map,

@@ -1,5 +1,5 @@
 // lds_dma.h -- device helpers shared by the LDS-DMA GEMM kernels
-// (gemm_bf16x6.hip, gemm_f16x3.hip).
+// (the bf16x6 GEMMs, gemm_bf16.hip, gemm_f16x3.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

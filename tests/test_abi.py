@@ -46,21 +46,38 @@ def test_only_gfx950_code_objects():
 
 
 def test_product_library_has_no_ablation_kernels():
-    """The DIAG ablation builds of the bf16x6 GEMM (wrong results, timing
-    only) are compiled only into `make EXPERIMENTS=1`'s separate library: no
-    gemm_bf16x6f_kernel instantiation in the product library has a non-zero
-    DIAG template argument (the third one), and the experiment-only tilings
-    are absent too."""
+    """The product library carries the bf16x6 kernels its dispatch
+    (kernels/gemm_bf16x6.hip) can reach and no other: the measurement
+    variants and the DIAG ablation builds (wrong results, timing only) are
+    compiled only into `make EXPERIMENTS=1`'s separate library
+    (kernels/gemm_bf16x6_exp.hip).  Exactly seven kernels: the direct-weight
+    kernel d on 128 x 128 tiles (the gathered FIRST layer, and wide tiles)
+    and on 256 x 128, the one-wave-per-SIMD kernel w on 512 x 128, the plane
+    kernel q with fp32 and with split output, and splice_pad_split.  Every d
+    has DIAG = 0, KS = 1, PIN = OUT16 = false; there is no f, ws or r
+    kernel."""
     data = open(os.path.join(ROOT, "catears_amd", "lib", "libcatears_hip.so"), "rb").read()
-    inst = re.findall(rb"gemm_bf16x6f_kernelINS0_5X6CfgI(?:Li\d+E)+EELi(\d+)ELi(\d+)E", data)
-    assert inst, "no bf16x6 kernel found"
-    assert all(diag == b"0" for _, diag in inst), sorted(set(inst))
-    # SCHED 6 (variant 55) and the 128 x 256 warp-specialised forms are experiments
-    assert not any(sched == b"6" for sched, _ in inst)
-    assert b"gemm_bf16x6ws_kernelINS0_5X6CfgILi128ELi256E" not in data
-    # the int8 GEMM's ablation builds (last template argument DIAG) likewise,
-    # and the register-direct bf16x6 schedule (measured slower) is an
-    # experiment too
+    syms = set(re.findall(rb"_ZN7catears12_GLOBAL__N_1\d+(?:gemm_bf16x6\w*?_kernel|splice_pad_split_kernel)\w*", data))
+    # name + template arguments of each: the scope in front and the return
+    # type and parameter list behind cut off
+    kern = sorted({re.sub(rb"^_ZN7catears12_GLOBAL__N_1\d+", b"", re.sub(rb"EEvNS0_6X6ArgsE$|EPKf\w+$", b"", s))
+                   for s in syms})
+    x6, w6 = b"INS0_5X6CfgI", b"INS0_5W6CfgI"
+    assert kern == sorted([
+        b"gemm_bf16x6d_kernel" + x6 + b"Li128ELi128ELi2ELi4ELi2EEELb1ELi0ELi1ELb0ELb0E",
+        b"gemm_bf16x6d_kernel" + x6 + b"Li128ELi128ELi2ELi4ELi2EEELb0ELi0ELi1ELb0ELb0E",
+        b"gemm_bf16x6d_kernel" + x6 + b"Li256ELi128ELi4ELi2ELi2EEELb0ELi0ELi1ELb0ELb0E",
+        b"gemm_bf16x6w_kernel" + w6 + b"Li512ELi128ELi4ELi2EEELb1ELi4E",
+        b"gemm_bf16x6q_kernel" + x6 + b"Li128ELi128ELi4ELi2ELi3EEELb1ELi0E",
+        b"gemm_bf16x6q_kernel" + x6 + b"Li128ELi128ELi4ELi2ELi3EEELb0ELi0E",
+        b"splice_pad_split_kernel",
+    ]), kern
+    for gone in (b"gemm_bf16x6f_kernel", b"gemm_bf16x6ws_kernel", b"gemm_bf16x6r_kernel"):
+        assert gone not in data, gone
+    # every d: <Cfg, FIRST, DIAG = 0, KS = 1, PIN = false, OUT16 = false>
+    d = re.findall(rb"gemm_bf16x6d_kernelINS0_5X6CfgI(?:Li\d+E)+EELb[01]E(Li\d+E)(Li\d+E)(Lb[01]E)(Lb[01]E)", data)
+    assert d and set(d) == {(b"Li0E", b"Li1E", b"Lb0E", b"Lb0E")}, sorted(set(d))
+    # the int8 GEMM's ablation builds (last template argument DIAG) likewise
     i8 = re.findall(rb"gemm_i8_glds_kernelILi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi(\d+)E", data)
     assert i8, "no int8 LDS-DMA GEMM found"
     assert set(i8) == {b"0"}, sorted(set(i8))
