@@ -40,7 +40,7 @@ HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc
            $(SRC)/nnet_programs.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
         $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
-HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_programs.h
+HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_i8_kernels.h $(SRC)/nnet_programs.h
 
 all: $(LIB) oracle
 

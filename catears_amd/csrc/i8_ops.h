@@ -99,6 +99,18 @@ __device__ __forceinline__ int byte_sum(int w) {
   return ((int)(u << 24) >> 24) + ((int)(u << 16) >> 24) + ((int)(u << 8) >> 24) + (w >> 24);
 }
 
+// p.off[seg] of a GEMM's argument struct through a select chain: a runtime
+// index into the kernel argument's array can force the whole argument struct
+// into scratch memory (the readfirstlane keeps the compiler from turning the
+// chain back into a load from a selected address)
+template <class Args>
+__device__ __forceinline__ int seg_off(const Args &p, int seg) {
+  int v = __builtin_amdgcn_readfirstlane(p.off[0]);
+#pragma unroll
+  for (int i = 1; i < 8; ++i) v = seg >= i ? __builtin_amdgcn_readfirstlane(p.off[i]) : v;
+  return v;
+}
+
 // Row sum of spliced row `row` of a layer input of m rows: the sum over the
 // segments of the row sums of rows clamp(row + off[sg], 0, m - 1), modulo
 // 2^32.  Static indices into off (a runtime index into a kernel argument's

@@ -64,15 +64,6 @@ struct LatArgs {
   int per, tiles_n, row_tiles;
 };
 
-// off[seg] through a select chain (a runtime index into the kernel argument's
-// array can force the whole argument struct into scratch memory)
-__device__ __forceinline__ int lat_seg_off(const LatArgs &p, int seg) {
-  int v = __builtin_amdgcn_readfirstlane(p.off[0]);
-#pragma unroll
-  for (int i = 1; i < 8; ++i) v = seg >= i ? __builtin_amdgcn_readfirstlane(p.off[i]) : v;
-  return v;
-}
-
 template <int PER>
 __global__ __launch_bounds__(64 * kNW) void i8_lat_gemm_kernel(LatArgs p) {
   constexpr int NT = 64 * kNW;
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(64 * kNW) void i8_lat_gemm_kernel(LatArgs p) {
     if (row < 16 * nsub && c < 4 * nk) {
       const int k = 64 * ks0 + 16 * c;
       const int seg = k / p.din, kc = k - seg * p.din;
-      int src = m0 + row + lat_seg_off(p, seg);
+      int src = m0 + row + seg_off(p, seg);
       src = src < 0 ? 0 : (src > p.m - 1 ? p.m - 1 : src);
       i32x4 v = (i32x4){0, 0, 0, 0};
       if (seg < p.nseg) v = *reinterpret_cast<const i32x4 *>(p.a + (int64_t)src * p.lda + kc);

@@ -56,6 +56,10 @@ I8_GEOMETRIES.update({
 # geometry -> (Linear index, kinds) of stand-alone row ops behind that Linear
 ROW_OPS = {"I5": (1, ("batchnorm", "relu"))}
 
+# what every kept CATEARS_I8_GEMM variant of the experiments library scores
+# (tests/test_gpu_i8_variants.py; test_i8ref.py shows what these reach)
+VARIANT_GEOMS, VARIANT_ROWS = ("I1", "I3"), (70, 300)
+
 HELD = ("A", "C", "E", "I1", "I3", "I4", "I5")     # the held-row tests' geometries
 FINALIZE = ("F4100", "F4099", "I2")                # with a LogSoftmax and a prior
 

@@ -55,7 +55,9 @@ def test_product_library_has_no_ablation_kernels():
     and on 256 x 128, the one-wave-per-SIMD kernel w on 512 x 128, the plane
     kernel q with fp32 and with split output, and splice_pad_split.  Every d
     has DIAG = 0, KS = 1, PIN = OUT16 = false; there is no f, ws or r
-    kernel."""
+    kernel.  The int8 GEMM likewise (kernels/nnet_i8.hip against
+    kernels/nnet_i8_exp.hip): exactly gemm_i8_pipe_kernel<256, 128, 3, 4, 2,
+    false> and the two Quantize kernels."""
     data = open(os.path.join(ROOT, "catears_amd", "lib", "libcatears_hip.so"), "rb").read()
     syms = set(re.findall(rb"_ZN7catears12_GLOBAL__N_1\d+(?:gemm_bf16x6\w*?_kernel|splice_pad_split_kernel)\w*", data))
     # name + template arguments of each: the scope in front and the return
@@ -77,10 +79,19 @@ def test_product_library_has_no_ablation_kernels():
     # every d: <Cfg, FIRST, DIAG = 0, KS = 1, PIN = false, OUT16 = false>
     d = re.findall(rb"gemm_bf16x6d_kernelINS0_5X6CfgI(?:Li\d+E)+EELb[01]E(Li\d+E)(Li\d+E)(Lb[01]E)(Lb[01]E)", data)
     assert d and set(d) == {(b"Li0E", b"Li1E", b"Lb0E", b"Lb0E")}, sorted(set(d))
-    # the int8 GEMM's ablation builds (last template argument DIAG) likewise
-    i8 = re.findall(rb"gemm_i8_glds_kernelILi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi\d+ELi(\d+)E", data)
-    assert i8, "no int8 LDS-DMA GEMM found"
-    assert set(i8) == {b"0"}, sorted(set(i8))
+    # the int8 GEMM likewise (kernels/nnet_i8.hip): the one kernel
+    # launch_i8_gemm launches and the two Quantize kernels; the plain LDS-DMA
+    # kernel with its DIAG ablation builds, the first kernel (once the
+    # fallback) and the removed ones are not in the library at all
+    syms = set(re.findall(rb"_ZN7catears12_GLOBAL__N_1\d+(?:gemm_i8_\w*?_kernel|quantize\w*?_kernel)\w*", data))
+    # (kernels/quant.hip's u8 quantize_kernel shares the name: one entry)
+    i8 = sorted({re.sub(rb"^_ZN7catears12_GLOBAL__N_1\d+", b"",
+                        re.sub(rb"(?:EEv|E)(?:NS0_6I8ArgsE|PKf\w+)$", b"", s)) for s in syms})
+    assert i8 == sorted([b"gemm_i8_pipe_kernelILi256ELi128ELi3ELi4ELi2ELb0E", b"quantize_kernel",
+                         b"quantize_fast_kernelILi1E"]), i8
+    for gone in (b"gemm_i8_glds_kernel", b"gemm_i8_nnet_kernel", b"gemm_i8_q_kernel", b"gemm_i8_reg_kernel",
+                 b"quantize_fast_kernelILi2E"):
+        assert gone not in data, gone
     assert b"gemm_i8_pipe_kernel" in data and b"lat_gemm_kernel" in data
     assert b"gemm_bf16x6r_kernel" not in data
 

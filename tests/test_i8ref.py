@@ -189,12 +189,43 @@ def test_central_half_ranges_clamp_both_ends(oracle, geom):
 
 
 def test_the_fallback_gemm_is_unreachable():
-    """launch_i8_gemm's gemm_i8_nnet_kernel branch needs kpad, the loader's
-    segment width or the operand's row stride off a multiple of 128 / 16:
-    quantize_weights pads K to 128 and splices every layer whose segments are
-    not whole K-tiles, so no layer of any geometry gets there."""
+    """launch_i8_gemm returns CE_GPU_EINVAL when kpad, the loader's segment
+    width or the operand's row stride is off a multiple of 128 / 128 / 16 (the
+    branch once launched gemm_i8_nnet_kernel, now the experiments library's
+    variant 0): quantize_weights pads K to 128 and splices every layer whose
+    segments are not whole K-tiles, so no layer of any geometry gets there."""
     for form in ("dynamic", "static", "static-latency"):
         assert not any(p["fallback_gemm"] for _, _, p in _all_paths(form))
+
+
+def test_variant_cases_cover_the_gemm_paths():
+    """What tests/test_gpu_i8_variants.py runs on every kept int8 GEMM variant
+    (i8ref.VARIANT_GEOMS x VARIANT_ROWS, dynamic and static) reaches both
+    operand forms, the segment changing on every K-tile, the three epilogues,
+    the fused min / max in the vector and in the scalar epilogue, one partial
+    row tile and two row tiles with a ragged second one, and more than one
+    column tile."""
+    I8_VARIANT_GEOMS, I8_VARIANT_ROWS = i8ref.VARIANT_GEOMS, i8ref.VARIANT_ROWS
+    assert (I8_VARIANT_GEOMS, I8_VARIANT_ROWS) == (("I1", "I3"), (70, 300))
+    P = {form: [(g, rows, p) for g in I8_VARIANT_GEOMS for rows in I8_VARIANT_ROWS
+                for p in i8ref.paths(i8ref.net(g), rows, form)] for form in ("dynamic", "static")}
+    for form, ps in P.items():
+        assert {p["operand"] for _, _, p in ps} == {"gathered", "spliced"}, form
+        # 8 asymmetric segments of one K-tile each: the loader's offsets change on every K-tile
+        assert any(p["operand"] == "gathered" and p["nseg"] == 8 and p["din"] == i8ref.K_ALIGN and
+                   p["ktiles"] == 8 and _asymmetric(p["off"]) for _, _, p in ps), form
+        for rows, tiles_m in ((70, 1), (300, 2)):
+            m = {rows + sum(netgen.context(i8ref.net(g))) for g in I8_VARIANT_GEOMS}
+            assert all(i8ref.TILE_M * (tiles_m - 1) < v < i8ref.TILE_M * tiles_m for v in m), (rows, m)
+            assert {p["tiles_m"] for _, r, p in ps if r == rows} == {tiles_m}, (form, rows)
+        assert any(p["tiles_n"] > 1 for _, _, p in ps), form
+        assert not any(p["fallback_gemm"] for _, _, p in ps), form
+    dyn, sta = P["dynamic"], P["static"]
+    assert {p["epilogue"] for _, _, p in dyn} == {"vector", "scalar"}
+    assert {p["epilogue"] for _, _, p in dyn if p["fused_minmax"]} == {"vector", "scalar"}
+    assert any(p["n"] == 100 and p["epilogue"] == "vector" and p["minmax"] == "fused" for g, _, p in dyn if g == "I1")
+    assert any(p["n"] == 130 and p["epilogue"] == "scalar" and p["operand"] == "spliced" for g, _, p in dyn if g == "I3")
+    assert {p["epilogue"] for _, _, p in sta} == {"requantize", "vector", "scalar"}
 
 
 # --------------------------------------------------------------- sharpness --

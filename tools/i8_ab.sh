@@ -1,7 +1,7 @@
 # int8 GEMM variants: parity (tests/test_gpu_int8.py) then the C5 bench, per CATEARS_I8_GEMM value
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" && mkdir -p gpurun_out/i8ab
-for v in ${VARIANTS:-15 20}; do
+for v in ${VARIANTS:-15 16}; do
   CATEARS_I8_GEMM=$v timeout -k 10 300 python -m pytest tests/test_gpu_int8.py tests/test_gpu_parity.py -q -m gpu -p no:cacheprovider -k "int8 or u8" > gpurun_out/i8ab/v$v.pytest.log 2>&1; rc=$?
   echo "variant $v pytest rc=$rc $(tail -1 gpurun_out/i8ab/v$v.pytest.log)"
   [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc

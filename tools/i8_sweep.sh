@@ -2,7 +2,7 @@
 # CATEARS_I8_GEMM variant in VARIANTS.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" && mkdir -p gpurun_out && export TMPDIR=/tmp
-for v in ${VARIANTS:-9 7 0}; do
+for v in ${VARIANTS:-16 15 0}; do
   rm -rf gpurun_out/i8v$v
   CATEARS_I8_GEMM=$v timeout -k 10 300 python -m pytest tests/test_gpu_int8.py -q -m gpu -p no:cacheprovider > gpurun_out/i8v$v.pytest.log 2>&1; rc=$?
   echo "variant $v pytest rc=$rc $(tail -1 gpurun_out/i8v$v.pytest.log)"
