@@ -225,18 +225,26 @@ static int upload_weight_images(const std::vector<float> &wt, GemmLayer *g, bool
 // K-tile of 32 inside one splice segment after the first layer (whose
 // spliced block is written padded), output widths multiples of 4.
 // m->x3_ok on entry: every weight matrix has its f16x3 image.
+// A row step of its own puts the program outside, unless the model was
+// admitted (ce_gpu_model_admit_row_ops): the rule then looks at the GEMM
+// steps only, and the model takes CE_GPU_GEMM_BF16X6 and CE_GPU_GEMM_BF16
+// but neither plane mode.
 static int settle_gemm_mode(ce_gpu_model *m) {
   m->x6_ok = true;
+  const bool row_steps = has_row_steps(m);
   for (size_t i = 0; i < m->steps.size(); ++i) {
     const Step &st = m->steps[i];
-    if (!st.is_gemm || st.gemm.n % 4 != 0 || (i > 0 && st.gemm.din % 32 != 0) || st.gemm.kpad % 32 != 0)
-      m->x6_ok = false;
+    if (!st.is_gemm) {
+      if (!m->row_ops_admitted) m->x6_ok = false;
+      continue;
+    }
+    if (st.gemm.n % 4 != 0 || (i > 0 && st.gemm.din % 32 != 0) || st.gemm.kpad % 32 != 0) m->x6_ok = false;
   }
-  m->x3_ok = m->x3_ok && m->x6_ok;
+  m->x3_ok = m->x3_ok && m->x6_ok && !row_steps;
   const int want = default_gemm();
   if (want < 0) return fail(CE_GPU_EINVAL, "default GEMM mode: not one of 0 fp32, 1 bf16x6, 2 f16x3, 3 bf16x6p, 4 bf16");
   m->gemm = want == CE_GPU_GEMM_F16X3 && m->x3_ok   ? CE_GPU_GEMM_F16X3
-            : want == CE_GPU_GEMM_BF16X6_PLANES && m->x6_ok ? CE_GPU_GEMM_BF16X6_PLANES
+            : want == CE_GPU_GEMM_BF16X6_PLANES && m->x6_ok && !row_steps ? CE_GPU_GEMM_BF16X6_PLANES
             : want == CE_GPU_GEMM_BF16 && m->x6_ok ? CE_GPU_GEMM_BF16
             : want != CE_GPU_GEMM_FP32 && m->x6_ok ? CE_GPU_GEMM_BF16X6
                                                     : CE_GPU_GEMM_FP32;
@@ -747,10 +755,17 @@ int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_mo
   // gpu_pad_widths: the re-layout onto padded widths, before gpu_gemm
   int pad = 0;
   CE_TRY(read_gpu_pad_widths(cf, &pad));
+  // gpu_row_ops: the row steps admitted to the matrix-core programs, before both
+  int row_ops = 0;
+  CE_TRY(read_gpu_row_ops(cf, &row_ops));
   ce_gpu_model *m = nullptr;
   CE_TRY(load_model(ctx, nnet, prior, left, right, tid2pdf, &m));
   m->chunk = chunk;
   std::unique_ptr<ce_gpu_model> own(m);
+  if (row_ops) {
+    const int rc = ce_gpu_model_admit_row_ops(ctx, m);
+    if (rc != CE_GPU_OK) return fail(rc, cf.file + ": gpu_row_ops = 1: " + last_error());
+  }
   if (pad) {
     const int rc = ce_gpu_model_pad_widths(ctx, m);
     if (rc != CE_GPU_OK) return fail(rc, cf.file + ": gpu_pad_widths = 1: " + last_error());
@@ -791,6 +806,8 @@ int ce_gpu_model_set_gemm(ce_gpu_model *m, int mode) {
     return fail(CE_GPU_EINVAL, "unknown GEMM mode");
   if (mode != CE_GPU_GEMM_FP32 && !m->x6_ok)
     return fail(CE_GPU_ENOTSUP, "this nnet program cannot run on split planes (unfused row op or widths)");
+  if ((mode == CE_GPU_GEMM_F16X3 || mode == CE_GPU_GEMM_BF16X6_PLANES) && has_row_steps(m))
+    return fail(CE_GPU_ENOTSUP, "this nnet program has a row step of its own: GEMM modes fp32, bf16x6 and bf16 only");
   if (mode == CE_GPU_GEMM_F16X3 && !m->x3_ok)
     return fail(CE_GPU_ENOTSUP, "a weight matrix is not finite: no f16x3 image");
   m->gemm = mode;
@@ -1285,19 +1302,25 @@ int ce_gpu_model_pad_widths(ce_gpu_ctx *ctx, ce_gpu_model *m) {
   if (!ctx || !m) return fail(CE_GPU_EINVAL, "NULL argument");
   if (m->int8) return fail(CE_GPU_EINVAL, "model_pad_widths: the model is quantized");
   if (m->x6_ok) return CE_GPU_OK;  // already inside the plane modes' envelope (or padded)
-  for (const Step &st : m->steps)
-    if (!st.is_gemm) return fail(CE_GPU_ENOTSUP, "model_pad_widths: the program has an unfused row op");
+  if (!m->row_ops_admitted && has_row_steps(m))
+    return fail(CE_GPU_ENOTSUP, "model_pad_widths: the program has an unfused row op");
   CE_HIP(hipSetDevice(ctx->device));
   CE_HIP(hipStreamSynchronize(ctx->stream));
   // the new layers are built beside the old ones: a failure leaves the model as it was
   const size_t nl = m->steps.size();
+  size_t last_gemm = 0;
+  for (size_t i = 0; i < nl; ++i)
+    if (m->steps[i].is_gemm) last_gemm = i;
   std::vector<GemmLayer> pad(nl);
   bool f16_all = true;
   int prev_n = 0, max_width = 0;
   for (size_t i = 0; i < nl; ++i) {
+    // an admitted model's row steps stay as they are: dim and the BatchNorm
+    // vectors at the true width, on rows whose leading dimension is padded
+    if (!m->steps[i].is_gemm) continue;
     const GemmLayer &g = m->steps[i].gemm;
     GemmLayer &p = pad[i];
-    const int round = i + 1 == nl ? 4 : 32;
+    const int round = i == last_gemm ? 4 : 32;
     p.n = (g.n + round - 1) / round * round;
     p.din = i == 0 ? g.din : prev_n;
     p.din_true = g.din;
@@ -1334,11 +1357,38 @@ int ce_gpu_model_pad_widths(ce_gpu_ctx *ctx, ce_gpu_model *m) {
     prev_n = p.n;
     max_width = std::max(max_width, p.n);
   }
-  for (size_t i = 0; i < nl; ++i) m->steps[i].gemm = std::move(pad[i]);
+  for (size_t i = 0; i < nl; ++i)
+    if (m->steps[i].is_gemm) m->steps[i].gemm = std::move(pad[i]);
   m->max_width = max_width;
   m->padded = true;
   m->x3_ok = f16_all;
   return settle_gemm_mode(m);
+}
+
+int ce_gpu_model_admit_row_ops(ce_gpu_ctx *ctx, ce_gpu_model *m) {
+  if (!ctx || !m) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (m->int8) return fail(CE_GPU_EINVAL, "model_admit_row_ops: the model is quantized (the int8 programs run row steps as they are)");
+  if (m->row_ops_admitted || !has_row_steps(m)) return CE_GPU_OK;
+  m->row_ops_admitted = true;
+  return settle_gemm_mode(m);
+}
+
+int ce_gpu_debug_rowop_chain(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int rows, int dim, float *d_x, int ld,
+                             const float *const *h_scale, const float *const *h_offset, uint16_t *d_out16, int ld16,
+                             int width16) {
+  if (!ctx || n_ops < 0 || n_ops > kRowChainMax || (n_ops > 0 && !h_ops) || rows < 0 || dim < 0)
+    return fail(CE_GPU_EINVAL, "bad argument");
+  if (rows == 0 || dim == 0) return CE_GPU_OK;
+  if (!d_x) return fail(CE_GPU_EINVAL, "NULL argument");
+  RowChain ch;
+  ch.n = n_ops;
+  ch.dim = dim;
+  for (int q = 0; q < n_ops; ++q) {
+    ch.kind[q] = h_ops[q];
+    ch.scale[q] = h_scale ? h_scale[q] : nullptr;
+    ch.offset[q] = h_offset ? h_offset[q] : nullptr;
+  }
+  return launch_rowop_chain(ctx->stream, ch, d_x, ld, rows, d_out16, ld16, width16);
 }
 
 int ce_gpu_model_padded_widths(const ce_gpu_model *m, int *h_true, int *h_padded, int capacity, int *count) {

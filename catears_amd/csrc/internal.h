@@ -277,6 +277,16 @@ struct RowOp {
   DevBuf scale, offset;  // BatchNorm
 };
 
+// Up to kRowChainMax consecutive row steps of one width, applied by one
+// launch_rowop_chain launch.
+constexpr int kRowChainMax = 4;
+struct RowChain {
+  int n = 0, dim = 0;
+  int kind[kRowChainMax] = {0, 0, 0, 0};
+  const float *scale[kRowChainMax] = {nullptr, nullptr, nullptr, nullptr};
+  const float *offset[kRowChainMax] = {nullptr, nullptr, nullptr, nullptr};
+};
+
 // One executable step of the nnet program.
 struct Step {
   bool is_gemm = true;
@@ -415,6 +425,9 @@ struct ce_gpu_model {
   bool x6_ok = false;                // program shape the bf16x6 / f16x3 paths take
   bool x3_ok = false;                // ... and every weight fits the f16x3 planes
   bool padded = false;               // ce_gpu_model_pad_widths re-laid the layers (GemmLayer::n_true)
+  // ce_gpu_model_admit_row_ops: the bf16x6 and bf16 programs run this model's
+  // row steps between their GEMMs (x6_ok then judges the GEMM steps only)
+  bool row_ops_admitted = false;
   std::vector<catears::Step> steps;  // all but the final log-softmax
   catears::DevBuf log_prior;         // num_pdfs
   std::vector<int32_t> tid2pdf;
@@ -442,6 +455,13 @@ struct ce_gpu_plan {
 };
 
 namespace catears {
+
+// The program has a row step of its own (a layer that is no Linear's epilogue).
+inline bool has_row_steps(const ce_gpu_model *m) {
+  for (const Step &st : m->steps)
+    if (!st.is_gemm) return true;
+  return false;
+}
 
 // Kernel launchers (kernels/*.hip).  All enqueue on `s` and return a status.
 int launch_fbank(hipStream_t s, const FbankTables *d_tab, const ce_gpu_plan *p, const float *pcm,
@@ -578,6 +598,14 @@ constexpr int kPropagateWindow = 1 << 16;
 int launch_finalize(hipStream_t s, const float *x, int ldx, int rows, int dim, bool log_softmax,
                     const float *log_prior, const int *row_dst, float *out);
 int launch_rowop(hipStream_t s, const RowOp &op, float *x, int ldx, int rows);
+// The steps of `ch` on rows of x (kernels/rowops.hip, rowop_chain_kernel):
+// launch_rowop's bits for each step in turn, in one pass.  In place over
+// ch.dim columns; with out16 the rows leave as bf16 (round to nearest even)
+// in out16 instead, width16 >= ch.dim columns of them (the columns behind
+// ch.dim converted as they are) -- rows wider than 4096 are then also worked
+// on in x.  ch.n == 0 with out16: the conversion alone.
+int launch_rowop_chain(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, uint16_t *out16 = nullptr,
+                       int ld16 = 0, int width16 = 0);
 int launch_trace_mark(hipStream_t s, int tag);
 int launch_loglik_gather(hipStream_t s, const float *ll, int rows, int ld, int dim, const int32_t *tpm, int n_tid,
                          const int32_t *row, const int32_t *trans, int n, float scale, float *out);

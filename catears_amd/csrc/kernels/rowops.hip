@@ -179,6 +179,191 @@ __global__ __launch_bounds__(256) void rowop_kernel(int kind, float *__restrict_
   }
 }
 
+// rowop_chain: up to kRowChainMax consecutive row steps of one width applied
+// to a row while it sits in registers -- one launch and one pass over HBM for
+// ReLU -> Normalize or BatchNorm -> ReLU -> Normalize instead of one per step
+// -- with rowop_kernel's arithmetic and summation order exactly: one wave per
+// row, lane l owns the columns c = l + 64 j (coalesced 4-byte accesses) and
+// sums them in ascending j, then wave_sum's xor tree.  A given fp32 row gives
+// rowop_kernel's bits whatever its leading dimension, alignment or place in
+// the block.
+//   OUT = float: in place, columns 0 .. dim - 1 (nothing beyond dim is read
+// into a sum or written).  OUT = uint16_t: the row leaves as bf16 (round to
+// nearest even, v_cvt_pk_bf16_f32) in another block, `width` >= dim columns
+// of it: the columns behind dim (a padded model's +0 columns) are converted
+// as they are.
+//   NJ columns per lane: every load of the row is issued (branch-free, on a
+// clamped column) before the first use.  Step q's kind sits in bits 4 q .. of
+// `kinds`; the steps' vectors are picked with static indices (a runtime index
+// into a kernel argument's array would put the argument into scratch).
+struct RowChainArgs {
+  const float *scale[kRowChainMax];
+  const float *offset[kRowChainMax];
+  int kinds, n, dim, width;
+};
+
+template <class OUT>
+__device__ __forceinline__ void store_row_value(OUT *o, float v) {
+  if constexpr (std::is_same<OUT, float>::value)
+    *o = v;
+  else
+    *o = __builtin_bit_cast(uint16_t, (__bf16)v);
+}
+
+template <class OUT, int NJ>
+__global__ __launch_bounds__(256) void rowop_chain_kernel(RowChainArgs a, float *x, int ldx, int rows, OUT *out, int ldo) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float *xr = x + (int64_t)row * ldx;
+  const int dim = a.dim, width = a.width;
+  float v[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) v[j] = xr[min(lane + 64 * j, width - 1)];
+#pragma unroll 1
+  for (int q = 0; q < a.n; ++q) {
+    const int kind = (a.kinds >> (4 * q)) & 15;
+    switch (kind) {
+      case kRowRelu:
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) v[j] = v[j] < 0.0f ? 0.0f : v[j];
+        break;
+      case kRowBatchNorm: {
+        const float *sc = q == 0 ? a.scale[0] : q == 1 ? a.scale[1] : q == 2 ? a.scale[2] : a.scale[3];
+        const float *of = q == 0 ? a.offset[0] : q == 1 ? a.offset[1] : q == 2 ? a.offset[2] : a.offset[3];
+        float t[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) t[j] = sc[min(lane + 64 * j, dim - 1)];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) v[j] = v[j] * t[j];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) t[j] = of[min(lane + 64 * j, dim - 1)];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) v[j] = v[j] + t[j];
+        break;
+      }
+      case kRowLogSoftmax: {
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) s += expf(v[j]);
+        const float ls = logf(wave_sum(s));
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) v[j] = v[j] - ls;
+        break;
+      }
+      case kRowSoftmax: {
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) {
+            v[j] = expf(v[j]);
+            s += v[j];
+          }
+        s = wave_sum(s);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) v[j] = v[j] / s;
+        break;
+      }
+      case kRowNormalize: {
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) s += v[j] * v[j];
+        s = wave_sum(s);
+        const float sc = (float)sqrt((double)(float)dim / (double)s);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (lane + 64 * j < dim) v[j] = v[j] * sc;
+        break;
+      }
+      default:
+        break;
+    }
+  }
+  OUT *o = out + (int64_t)row * ldo;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (lane + 64 * j < width) store_row_value(o + lane + 64 * j, v[j]);
+}
+
+// Rows wider than 64 * kMaxPerLane: the same steps as loops over the fp32
+// row in place (rowop_kernel's own loops: a lane reads back only what it
+// wrote), then the bf16 copy.
+template <class OUT>
+__global__ __launch_bounds__(256) void rowop_chain_loop_kernel(RowChainArgs a, float *x, int ldx, int rows, OUT *out,
+                                                               int ldo) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  float *xr = x + (int64_t)row * ldx;
+  const int dim = a.dim;
+#pragma unroll 1
+  for (int q = 0; q < a.n; ++q) {
+    const int kind = (a.kinds >> (4 * q)) & 15;
+    switch (kind) {
+      case kRowRelu:
+        for (int c = lane; c < dim; c += 64) xr[c] = xr[c] < 0.0f ? 0.0f : xr[c];
+        break;
+      case kRowBatchNorm: {
+        const float *sc = q == 0 ? a.scale[0] : q == 1 ? a.scale[1] : q == 2 ? a.scale[2] : a.scale[3];
+        const float *of = q == 0 ? a.offset[0] : q == 1 ? a.offset[1] : q == 2 ? a.offset[2] : a.offset[3];
+        for (int c = lane; c < dim; c += 64) {
+          float t = xr[c] * sc[c];
+          xr[c] = t + of[c];
+        }
+        break;
+      }
+      case kRowLogSoftmax: {
+        float s = 0.0f;
+        for (int c = lane; c < dim; c += 64) s += expf(xr[c]);
+        const float ls = logf(wave_sum(s));
+        for (int c = lane; c < dim; c += 64) xr[c] = xr[c] - ls;
+        break;
+      }
+      case kRowSoftmax: {
+        float s = 0.0f;
+        for (int c = lane; c < dim; c += 64) s += expf(xr[c]);
+        s = wave_sum(s);
+        for (int c = lane; c < dim; c += 64) xr[c] = expf(xr[c]) / s;
+        break;
+      }
+      case kRowNormalize: {
+        float s = 0.0f;
+        for (int c = lane; c < dim; c += 64) s += xr[c] * xr[c];
+        s = wave_sum(s);
+        const float sc = (float)sqrt((double)(float)dim / (double)s);
+        for (int c = lane; c < dim; c += 64) xr[c] = xr[c] * sc;
+        break;
+      }
+      default:
+        break;
+    }
+  }
+  if constexpr (!std::is_same<OUT, float>::value) {
+    OUT *o = out + (int64_t)row * ldo;
+    for (int c = lane; c < a.width; c += 64) store_row_value(o + c, xr[c]);
+  }
+}
+
+template <class OUT>
+int launch_rowop_chain_as(hipStream_t s, const RowChainArgs &a, float *x, int ldx, int rows, OUT *out, int ldo) {
+  const dim3 grid((rows + 3) / 4), block(256);
+  if (a.width <= 64 * 4)
+    hipLaunchKernelGGL((rowop_chain_kernel<OUT, 4>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+  else if (a.width <= 64 * 16)
+    hipLaunchKernelGGL((rowop_chain_kernel<OUT, 16>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+  else if (a.width <= 64 * kMaxPerLane)
+    hipLaunchKernelGGL((rowop_chain_kernel<OUT, kMaxPerLane>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+  else
+    hipLaunchKernelGGL((rowop_chain_loop_kernel<OUT>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+  CE_HIP(hipGetLastError());
+  return CE_GPU_OK;
+}
+
 // SpliceLayer::Propagate (src/nnet.cc:50-95): out[t] = concat over s of
 // in[clamp(t + idx[s], 0, rows - 1)].  One block per output row; a pure copy.
 struct SpliceIdx {
@@ -419,6 +604,29 @@ int launch_sum_f64(hipStream_t s, int count, const float *const *x, const int64_
 
 int launch_rowop(hipStream_t s, const RowOp &op, float *x, int ldx, int rows) {
   return launch_rowop_raw(s, op.kind, op.dim, op.scale.as<float>(), op.offset.as<float>(), x, ldx, rows);
+}
+
+int launch_rowop_chain(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, uint16_t *out16, int ld16,
+                       int width16) {
+  if (ch.n < 0 || ch.n > kRowChainMax) return fail(CE_GPU_EINVAL, "rowop_chain: 0..4 steps per launch");
+  const int width = out16 ? width16 : ch.dim;
+  if (ch.dim < 0 || ldx < width || (out16 && (width < ch.dim || ld16 < width)))
+    return fail(CE_GPU_EINVAL, "rowop_chain: a row does not hold its width");
+  if (rows <= 0 || width == 0 || (ch.n == 0 && !out16)) return CE_GPU_OK;
+  RowChainArgs a = {};
+  a.n = ch.dim > 0 ? ch.n : 0;
+  a.dim = ch.dim;
+  a.width = width;
+  for (int q = 0; q < a.n; ++q) {
+    if (ch.kind[q] < kRowRelu || ch.kind[q] > kRowNormalize) return fail(CE_GPU_EINVAL, "rowop_chain: unknown row op");
+    if (ch.kind[q] == kRowBatchNorm && (!ch.scale[q] || !ch.offset[q]))
+      return fail(CE_GPU_EINVAL, "rowop_chain: BatchNorm needs scale/offset");
+    a.kinds |= ch.kind[q] << (4 * q);
+    a.scale[q] = ch.scale[q];
+    a.offset[q] = ch.offset[q];
+  }
+  if (out16) return launch_rowop_chain_as<uint16_t>(s, a, x, ldx, rows, out16, ld16);
+  return launch_rowop_chain_as<float>(s, a, x, ldx, rows, x, ldx);
 }
 
 namespace {

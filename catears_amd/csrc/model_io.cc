@@ -237,6 +237,17 @@ int read_gpu_pad_widths(const Config &cf, int *pad) {
   return CE_GPU_OK;
 }
 
+int read_gpu_row_ops(const Config &cf, int *admit) {
+  *admit = 0;
+  auto it = cf.kv.find("gpu_row_ops");
+  if (it == cf.kv.end()) return CE_GPU_OK;
+  if (it->second != "0" && it->second != "1")
+    return fail(CE_GPU_EINVAL, cf.file + ": gpu_row_ops = " + it->second + ": not 0 or 1");
+  // beside gpu_int8_ranges: accepted, no effect (the int8 programs run row steps as they are)
+  *admit = it->second == "1";
+  return CE_GPU_OK;
+}
+
 // ------------------------------------------------------------------ NN02 --
 
 int read_nnet(Reader &rd, std::vector<RawLayer> *layers, int *hl, int *hr) {

@@ -96,6 +96,14 @@ int read_gpu_gemm(const Config &cf, int *mode);
 // beside gpu_int8_ranges (a padded model takes no int8 form), naming both keys.
 int read_gpu_pad_widths(const Config &cf, int *pad);
 
+// The configuration key gpu_row_ops = 0 | 1 (this implementation's own): 1
+// admits the loaded model's row steps to the matrix-core programs with
+// ce_gpu_model_admit_row_ops, before gpu_pad_widths and gpu_gemm are applied.
+// Absent: *admit = 0.  Any other value: CE_GPU_EINVAL with "gpu_row_ops =
+// <value>" in the text.  Beside gpu_int8_ranges it is accepted and has no
+// effect, like gpu_gemm.
+int read_gpu_row_ops(const Config &cf, int *admit);
+
 // Layer ids (src/nnet.h:21-30).
 enum LayerId { kLinear = 0, kReLU = 1, kNormalize = 2, kSoftmax = 3, kSplice = 6, kBatchNorm = 7,
                kLogSoftmax = 8, kNarrow = 9 };

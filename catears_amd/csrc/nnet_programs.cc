@@ -61,8 +61,9 @@ static int ensure_overflow_word(ce_gpu_ctx *ctx) {
 // buffers lie.  Offsets a program does not use stay 0.
 struct Layout {
   // ctx->workspace: two ping-pong activation blocks at 0 and `blk`; the
-  // operand-chain programs' fp32 output at `out`
-  size_t ws_floats = 0, blk = 0, out = 0;
+  // operand-chain programs' fp32 output at `out`; plain bf16's fp32 block
+  // ahead of row steps at `f32`
+  size_t ws_floats = 0, blk = 0, out = 0, f32 = 0;
   // ctx->scratch.  fp32: the first layer's spliced block.  int8: operand
   // buffers at 0 (and `xq_stride`, static), row-sum buffers at `rowsum` +
   // i * `rowsum_stride`, the dynamic program's parameters and min / max
@@ -193,12 +194,45 @@ static void fill_epilogue(Args &a, const GemmLayer &g) {
   a.npost = g.npost;
 }
 
-// The widest operand row of an all-GEMM program: a layer's padded K, or an
-// output rounded up to `round` columns for the layer that reads it.
+// The widest operand row of a matrix-core program: a Linear's padded K, or
+// its output rounded up to `round` columns for the layer that reads it.
 static int max_operand_width(const ce_gpu_model *m, int round) {
   int w = 0;
-  for (const Step &st : m->steps) w = std::max(w, std::max(st.gemm.kpad, (int)round_up(st.gemm.n, round)));
+  for (const Step &st : m->steps)
+    if (st.is_gemm) w = std::max(w, std::max(st.gemm.kpad, (int)round_up(st.gemm.n, round)));
   return w;
+}
+
+static size_t last_gemm_step(const ce_gpu_model *m) {
+  size_t last = 0;
+  for (size_t i = 0; i < m->steps.size(); ++i)
+    if (m->steps[i].is_gemm) last = i;
+  return last;
+}
+
+// The row steps at *si .. (up to the next Linear), in place on the fp32 rows
+// the Linear before them wrote: one launch_rowop_chain per kRowChainMax
+// steps.  With out16 the last launch leaves the rows as bf16 there instead,
+// width16 columns of them (the plain bf16 program's hand-over to the next
+// Linear).  *si ends on the next GEMM step, or behind the last step.
+static int run_row_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, size_t *si, float *x, int ldx, int rows,
+                         uint16_t *out16 = nullptr, int ld16 = 0, int width16 = 0) {
+  size_t end = *si;
+  while (end < m->steps.size() && !m->steps[end].is_gemm) ++end;
+  while (*si < end) {
+    RowChain ch;
+    ch.dim = m->steps[*si].row.dim;
+    for (; *si < end && ch.n < kRowChainMax; ++*si, ++ch.n) {
+      const RowOp &op = m->steps[*si].row;
+      ch.kind[ch.n] = op.kind;
+      ch.scale[ch.n] = op.scale.as<float>();
+      ch.offset[ch.n] = op.offset.as<float>();
+    }
+    const bool store16 = out16 && *si == end;
+    CE_TRY(launch_rowop_chain(ctx->stream, ch, x, ldx, rows, store16 ? out16 : nullptr, ld16, width16));
+    ctx->chain_end = nullptr;  // an untimed launch breaks a ProfChain
+  }
+  return CE_GPU_OK;
 }
 
 // ---------------------------------------------------------------- fp32 --
@@ -265,8 +299,13 @@ static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
       ldx = g.n;
       cur ^= 1;
       first = false;
-    } else {
+    } else if (!m->row_ops_admitted) {
       CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
+    } else if ((&st)[-1].is_gemm) {
+      // an admitted model (ce_gpu_model_admit_row_ops): the run of row steps
+      // that starts here in one launch per chain -- the same bits
+      size_t si = &st - m->steps.data();
+      CE_TRY(run_row_steps(ctx, m, &si, const_cast<float *>(x), ldx, rows));
     }
   }
   *y = x;
@@ -280,7 +319,7 @@ static int run_steps_f32(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
 // first layer gathers the caller's fp32 rows in its loader, every layer has
 // the fragment image, the later layers' segments are whole K-tiles.
 static bool x6f_planes_ok(const ce_gpu_model *m) {
-  bool ok = x6_plane_chain_env() != 0 && x6_first_direct() && m->steps[0].gemm.din % 8 == 0;
+  bool ok = x6_plane_chain_env() != 0 && x6_first_direct() && !has_row_steps(m) && m->steps[0].gemm.din % 8 == 0;
   for (size_t i = 0; ok && i < m->steps.size(); ++i)
     ok = m->steps[i].gemm.wdir.ptr && (i == 0 || m->steps[i].gemm.din % 32 == 0);
   return ok;
@@ -293,8 +332,9 @@ static Layout layout_x6f(const ce_gpu_model *m, int rows, bool latency, bool pla
   Layout L;
   L.blk = round_up((size_t)rows * max_operand_width(m, 32) * (planes ? 3 : 2) / 2, 64);
   L.out = 2 * L.blk;
-  L.ws_floats = L.out + (size_t)rows * m->steps.back().gemm.n;  // the last layer's leading dimension
+  L.ws_floats = L.out + (size_t)rows * m->steps[last_gemm_step(m)].gemm.n;  // the last Linear's leading dimension
   for (size_t i = 0; latency && i < m->steps.size(); ++i) {
+    if (!m->steps[i].is_gemm) continue;
     const GemmLayer &g = m->steps[i].gemm;
     const int kpad = i == 0 ? g.kpad : g.nseg * g.din;
     L.lat_words = std::max(L.lat_words, x6_lat_part_floats(rows, g.n, x6_lat_slices(kpad, g.n)));
@@ -315,9 +355,13 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
   const float *xs = nullptr;
   int px = 0, cur = 0;
   ProfChain chain(ctx);  // every step below is one launch; GEMMs back to back
-  for (size_t i = 0; i < m->steps.size(); ++i) {
+  const size_t last_gemm = last_gemm_step(m);
+  int linear = 0;
+  for (size_t i = 0; i < m->steps.size();) {
+    // every step is a Linear but for an admitted model's row steps, which the
+    // bottom of the loop runs behind the Linear they follow
     const GemmLayer &g = m->steps[i].gemm;
-    const bool last = i + 1 == m->steps.size();
+    const bool last = i == last_gemm;
     X6Gemm a;
     // calibration: the block entering this layer's Splice (the caller's rows,
     // or the previous layer's fp32 output)
@@ -344,8 +388,9 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
     } else {
       fill_geometry(a, g.din, g.nseg, off);
       // (never the plane chain: an experiments-library knob, off by default)
-      CE_TRY(exchange_input(ctx, inc, (int)i, xs, (size_t)px * 4, (size_t)px * 4));
+      CE_TRY(exchange_input(ctx, inc, linear, xs, (size_t)px * 4, (size_t)px * 4));
     }
+    ++linear;
     // planes into layer i / out of it: every layer after the first (mode 1),
     // or the output layer only (mode 2)
     const size_t nst = m->steps.size();
@@ -386,18 +431,24 @@ static int run_steps_x6f(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x,
         // the reduce may run inside the finalize -- which writes whole
         // float4 chunks of a row as wide as the partials, so not for a last
         // layer on a padded width (lat_reduce + launch_finalize then)
-        if (last && lat_fused_final() && g.n == m->num_pdfs) a.tail = tail;
+        // ... nor when row steps follow it: they need the reduced block
+        if (last && i + 1 == m->steps.size() && lat_fused_final() && g.n == m->num_pdfs) a.tail = tail;
         CE_TRY(launch_gemm_bf16x6_lat(ctx->stream, a, ctx->lat_part.as<float>(), pf, ctx->lat_tickets.as<unsigned>()));
       } else if (!(diag_skip() & (i == 0 ? 1 : last ? 16 : 32))) {
         CE_TRY(launch_gemm_bf16x6(ctx->stream, a));
       }
     }
+    ++i;
+    // row steps behind this Linear: in place on the fp32 block it wrote (in
+    // latency mode after the slice reduce), so the next Linear -- its tap and
+    // its cache exchange -- sees its input after them
+    CE_TRY(run_row_steps(ctx, m, &i, a.y32, a.ldy, rows));
     xs = buf[cur];
     px = pn;
     cur ^= 1;
   }
   *y = out;
-  *ldy = m->steps.back().gemm.n;
+  *ldy = m->steps[last_gemm].gemm.n;
   return CE_GPU_OK;
 }
 
@@ -469,13 +520,22 @@ struct ChainF16 {
   static int gemm(hipStream_t s, const Args &a) { return launch_gemm_f16x3(s, a); }
 };
 
-// Two blocks of rows x kWords x max_in 16-bit words and the fp32 output.
+// Two blocks of rows x kWords x max_in 16-bit words and the fp32 output;
+// behind it (`f32`) the fp32 block of the widest hidden Linear that row steps
+// follow (an admitted model in plain bf16: that Linear writes fp32, its row
+// steps hand the next Linear bf16).
 template <class Mode>
 static Layout layout_chain16(const ce_gpu_model *m, int rows) {
   Layout L;
   L.blk = round_up(((size_t)rows * Mode::kWords * max_operand_width(m, Mode::kRound) + 1) / 2, 64);
   L.out = 2 * L.blk;
-  L.ws_floats = L.out + (size_t)rows * m->steps.back().gemm.n;  // the last layer's leading dimension
+  const size_t last_gemm = last_gemm_step(m);
+  L.f32 = round_up(L.out + (size_t)rows * m->steps[last_gemm].gemm.n, 64);  // the last Linear's leading dimension
+  size_t hidden = 0;
+  for (size_t i = 0; i < last_gemm; ++i)
+    if (m->steps[i].is_gemm && !m->steps[i + 1].is_gemm)
+      hidden = std::max(hidden, round_up(m->steps[i].gemm.n, Mode::kRound));
+  L.ws_floats = hidden ? L.f32 + (size_t)rows * hidden : L.out + (size_t)rows * m->steps[last_gemm].gemm.n;
   L.overflow = Mode::kOverflow;
   return L;
 }
@@ -484,16 +544,25 @@ template <class Mode>
 static int run_steps_chain16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
                              const int *row_map, const float **y, int *ldy, const IncrChunk *inc = nullptr) {
   if (inc && !Mode::kIncremental) return fail(CE_GPU_ENOTSUP, "incremental chunk: not in this GEMM mode");
+  if (Mode::kWords != 1 && has_row_steps(m)) return fail(CE_GPU_ENOTSUP, "row steps: not on split planes");
   const Layout L = layout_chain16<Mode>(m, rows);
   CE_TRY(ensure_layout(ctx, L));
   uint16_t *sbuf[2] = {reinterpret_cast<uint16_t *>(ctx->workspace.as<float>()),
                        reinterpret_cast<uint16_t *>(ctx->workspace.as<float>() + L.blk)};
   float *out = ctx->workspace.as<float>() + L.out;
+  float *hid32 = ctx->workspace.as<float>() + L.f32;
   const uint16_t *xs = nullptr;
-  int px = 0, cur = 0;
-  for (size_t i = 0; i < m->steps.size(); ++i) {
+  int px = 0, cur = 0, linear = 0;
+  const size_t last_gemm = last_gemm_step(m);
+  for (size_t i = 0; i < m->steps.size();) {
+    // every step is a Linear but for an admitted model's row steps (plain
+    // bf16 only), which the bottom of the loop runs behind their Linear
     const GemmLayer &g = m->steps[i].gemm;
-    const bool last = i + 1 == m->steps.size();
+    const bool last = i == last_gemm;
+    // a hidden Linear with row steps behind it writes fp32, as the last one
+    // does; they run in fp32 and the last of them stores bf16 for the next
+    // Linear -- one rounding per value, by the consumer's rule
+    const bool rows_follow = i + 1 < m->steps.size() && !m->steps[i + 1].is_gemm;
     typename Mode::Args a;
     int off[8];
     layer_offsets(g, inc, off);
@@ -506,8 +575,9 @@ static int run_steps_chain16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float
       fill_geometry(a, g.kpad, 1, nullptr);
     } else {
       fill_geometry(a, g.din, g.nseg, off);
-      CE_TRY(exchange_input(ctx, inc, (int)i, xs, (size_t)px * Mode::kWords * 2, (size_t)px * Mode::kWords * 2));
+      CE_TRY(exchange_input(ctx, inc, linear, xs, (size_t)px * Mode::kWords * 2, (size_t)px * Mode::kWords * 2));
     }
+    ++linear;
     a.x = xs;
     a.ldx = Mode::kWords * px;
     if (Mode::kWords > 1) a.px = px;  // (a single plane has no plane stride)
@@ -520,6 +590,9 @@ static int run_steps_chain16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float
     if (last) {
       a.y32 = out;
       a.ldy = g.n;
+    } else if (rows_follow) {
+      a.y32 = hid32;
+      a.ldy = pn;
     } else {
       a.y16 = sbuf[cur];
       a.ldy = Mode::kWords * pn;
@@ -529,12 +602,15 @@ static int run_steps_chain16(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float
       ProfScope prof(ctx, CE_GPU_PROF_GEMM);
       CE_TRY(Mode::gemm(ctx->stream, a));
     }
+    ++i;
+    if (rows_follow)
+      CE_TRY(run_row_steps(ctx, m, &i, a.y32, a.ldy, rows, last ? nullptr : sbuf[cur], pn, pn));
     xs = sbuf[cur];
     px = pn;
     cur ^= 1;
   }
   *y = out;
-  *ldy = m->steps.back().gemm.n;
+  *ldy = m->steps[last_gemm].gemm.n;
   return CE_GPU_OK;
 }
 
@@ -744,7 +820,7 @@ int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, i
     if (tap || (m->int8 && !m->int8_static)) return fail(CE_GPU_EINVAL, "incremental chunk: unsupported form");
     if (m->int8) return run_steps_i8_static(ctx, m, x, ldx, rows, row_map, y, ldy, inc);
     if (m->gemm == CE_GPU_GEMM_BF16) return run_steps_chain16<ChainBf16>(ctx, m, x, ldx, rows, row_map, y, ldy, inc);
-    if (m->gemm == CE_GPU_GEMM_BF16X6 && x6_f32in() && x6_plane_chain_env() == 0)
+    if (m->gemm == CE_GPU_GEMM_BF16X6 && ((x6_f32in() && x6_plane_chain_env() == 0) || has_row_steps(m)))
       return run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail, nullptr, inc);
     if (m->gemm == CE_GPU_GEMM_FP32) return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy, nullptr, inc);
     return fail(CE_GPU_ENOTSUP, "incremental chunk: GEMM modes fp32, bf16x6 and bf16 only");
@@ -752,7 +828,7 @@ int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, i
   if (tap) {
     // calibration reads fp32 activations between the layers
     if (m->int8) return fail(CE_GPU_EINVAL, "model_calibrate: the model is already quantized");
-    if (m->gemm == CE_GPU_GEMM_BF16X6 && x6_f32in() && x6_plane_chain_env() == 0)
+    if (m->gemm == CE_GPU_GEMM_BF16X6 && ((x6_f32in() && x6_plane_chain_env() == 0) || has_row_steps(m)))
       return run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, nullptr, tap);
     if (m->gemm == CE_GPU_GEMM_FP32) return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy, tap);
     return fail(CE_GPU_ENOTSUP, "model_calibrate: GEMM modes fp32 and bf16x6 only (the others keep activations as planes)");
@@ -763,7 +839,7 @@ int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, i
   if (m->gemm == CE_GPU_GEMM_BF16) return run_steps_chain16<ChainBf16>(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->gemm == CE_GPU_GEMM_BF16X6_PLANES) return run_steps_chain16<ChainX6>(ctx, m, x, ldx, rows, row_map, y, ldy);
   if (m->gemm == CE_GPU_GEMM_BF16X6)
-    return x6_f32in() ? run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail)
+    return x6_f32in() || has_row_steps(m) ? run_steps_x6f(ctx, m, x, ldx, rows, row_map, y, ldy, tail)
                       : run_steps_chain16<ChainX6>(ctx, m, x, ldx, rows, row_map, y, ldy);
   return run_steps_f32(ctx, m, x, ldx, rows, row_map, y, ldy);
 }
@@ -807,14 +883,15 @@ int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows) {
     return ensure_layout(ctx, all);
   }
   cover(&all, layout_f32(m, rows));
-  bool all_gemm = true;
-  for (const Step &st : m->steps) all_gemm = all_gemm && st.is_gemm;
-  if (m->x6_ok && all_gemm) {
+  if (m->x6_ok) {
     cover(&all, layout_x6f(m, rows, true, false));
     cover(&all, layout_x6f(m, rows, false, x6f_planes_ok(m)));
-    cover(&all, layout_chain16<ChainX6>(m, rows));
     cover(&all, layout_chain16<ChainBf16>(m, rows));
-    cover(&all, layout_chain16<ChainF16>(m, rows));
+    // the plane modes take no model with a row step
+    if (!has_row_steps(m)) {
+      cover(&all, layout_chain16<ChainX6>(m, rows));
+      cover(&all, layout_chain16<ChainF16>(m, rows));
+    }
   }
   return ensure_layout(ctx, all);
 }

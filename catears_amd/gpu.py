@@ -41,6 +41,7 @@ ABI = [
     "ce_gpu_gemm_mode_from_name",
     "ce_gpu_sessions_create_ex", "ce_gpu_sessions_stats",
     "ce_gpu_model_pad_widths", "ce_gpu_model_padded_widths",
+    "ce_gpu_model_admit_row_ops", "ce_gpu_debug_rowop_chain",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -134,6 +135,8 @@ def lib():
         "ce_gpu_i8_latency_plan": (ci, [ci, ci, ci, pi, pi]),
         "ce_gpu_debug_i8_latency_launches": (ci, [pi64]),
         "ce_gpu_model_pad_widths": (ci, [vp, vp]),
+        "ce_gpu_model_admit_row_ops": (ci, [vp, vp]),
+        "ce_gpu_debug_rowop_chain": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci]),
         "ce_gpu_model_padded_widths": (ci, [vp, vp, vp, ci, pi]),
     }
     for name, (res, args) in sig.items():
@@ -326,6 +329,15 @@ class Model:
         Nothing changes for a model already inside the envelope
         (ce_gpu_model_pad_widths)."""
         check(lib().ce_gpu_model_pad_widths(ctx.h, self.h))
+        return self
+
+    def admit_row_ops(self, ctx):
+        """Admit the model's row steps (Normalize, Softmax, a post chain too
+        long to fuse) to the matrix-core programs: the model then takes the
+        modes fp32, bf16x6 and bf16, latency mode and pad_widths, and is in
+        the mode it would have loaded in.  Nothing changes for a model
+        without a row step (ce_gpu_model_admit_row_ops)."""
+        check(lib().ce_gpu_model_admit_row_ops(ctx.h, self.h))
         return self
 
     def padded_widths(self):
@@ -806,6 +818,23 @@ def rowwise(ctx, op, x, scale=None, offset=None):
     check(lib().ce_gpu_rowwise(ctx.h, ROW_OPS[op], x.shape[0], x.shape[1], _ptr_rows(x), x.stride(0), _ptr(scale),
                                _ptr(offset)))
     return x
+
+
+def rowop_chain(ctx, ops, x, dim=None, vectors=None, out16=None):
+    """ce_gpu_debug_rowop_chain: the row ops `ops` (ROW_OPS names, at most 4)
+    in one launch on the first `dim` columns of x's rows, in place;
+    vectors[q] = (scale, offset) for a BatchNorm.  out16: an int16 / uint16 /
+    bfloat16 device tensor of x's rows that takes the rows as bf16 instead
+    (all its columns).  Returns out16 if given, else x."""
+    dim = x.shape[1] if dim is None else dim
+    n = len(ops)
+    kinds = (ctypes.c_int * max(n, 1))(*[ROW_OPS[o] for o in ops])
+    sc = (ctypes.c_void_p * max(n, 1))(*[_ptr(vectors[q][0]) if vectors and vectors[q] else None for q in range(n)])
+    of = (ctypes.c_void_p * max(n, 1))(*[_ptr(vectors[q][1]) if vectors and vectors[q] else None for q in range(n)])
+    o16, ld16, w16 = (None, 0, 0) if out16 is None else (_ptr_rows(out16), out16.stride(0), out16.shape[1])
+    check(lib().ce_gpu_debug_rowop_chain(ctx.h, n, kinds, x.shape[0], dim, _ptr_rows(x), x.stride(0), sc, of, o16,
+                                         ld16, w16))
+    return x if out16 is None else out16
 
 
 def quantize(ctx, x, q=None):

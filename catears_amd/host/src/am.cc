@@ -95,6 +95,22 @@ Status AcousticModel::Read(const Configuration &conf) {
   if (rc != CE_GPU_OK) return Status::Corruption(util::Format("{}: {}", nnet_file, ce_gpu_last_error()));
   int pdfs = 0;
   ce_gpu_model_info(model_, nullptr, nullptr, &feat_dim_, &pdfs, nullptr, nullptr);
+  // gpu_row_ops = 1: the model's row steps (Normalize, Softmax, a post chain
+  // too long to fuse) admitted to the matrix-core programs
+  // (ce_gpu_model_admit_row_ops), before gpu_pad_widths and gpu_gemm.
+  // Beside gpu_int8_ranges it is accepted and has no effect.
+  const std::string row_ops = conf.GetStringOrElse("gpu_row_ops", "0");
+  if (row_ops != "0" && row_ops != "1") {
+    ce_gpu_model_destroy(model_);
+    model_ = nullptr;
+    return Status::Corruption(util::Format("gpu_row_ops = {}: not 0 or 1", row_ops));
+  }
+  if (row_ops == "1" && ce_gpu_model_admit_row_ops(rt.ctx(), model_) != CE_GPU_OK) {
+    const std::string why = util::Format("gpu_row_ops = 1: {}", ce_gpu_last_error());
+    ce_gpu_model_destroy(model_);
+    model_ = nullptr;
+    return Status::Corruption(why);
+  }
   // gpu_pad_widths = 1: the model re-laid onto padded layer widths
   // (ce_gpu_model_pad_widths), before gpu_gemm, so that every GEMM mode and
   // latency mode take a net of any width.  Not beside gpu_int8_ranges: a

@@ -82,7 +82,9 @@ const char *ce_gpu_last_error(void);
  * key gpu_gemm), and so do the incremental session sets
  * (ce_gpu_sessions_create_ex, ce_gpu_sessions_stats), and so does the
  * re-layout onto padded widths (ce_gpu_model_pad_widths,
- * ce_gpu_model_padded_widths, the config key gpu_pad_widths). */
+ * ce_gpu_model_padded_widths, the config key gpu_pad_widths), and so do the
+ * row steps in the matrix-core programs (ce_gpu_model_admit_row_ops,
+ * ce_gpu_debug_rowop_chain, the config key gpu_row_ops). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -225,6 +227,18 @@ int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees);
  * (i8_lat_gemm_kernel; counted on the host when one is enqueued): shows which
  * of the two int8 kernels a call took.  Measurement plumbing as above. */
 int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
+/* One launch of the kernel behind an admitted model's row steps
+ * (ce_gpu_model_admit_row_ops), for tests and tools: the n_ops <= 4 row ops
+ * h_ops (CE_GPU_ROW_*; h_scale[q] / h_offset[q] device vectors of a
+ * BatchNorm) applied in turn to `rows` rows of `dim` columns of d_x, leading
+ * dimension ld, in place -- the bits of ce_gpu_rowwise called once per op.
+ * With d_out16 the rows leave as bf16 (round to nearest even) there instead,
+ * width16 >= dim columns at leading dimension ld16 (the columns behind dim
+ * converted as they are; d_x is then working memory).  Enqueues on the
+ * context's stream.  Measurement plumbing as above. */
+int ce_gpu_debug_rowop_chain(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int rows, int dim, float *d_x, int ld,
+                             const float *const *h_scale, const float *const *h_offset, uint16_t *d_out16, int ld16,
+                             int width16);
 
 /* -------------------------------------------------------------- model --- */
 
@@ -249,6 +263,10 @@ int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
  * works on a model of any width; a value other than 0 or 1, or the value 1
  * beside gpu_int8_ranges, fails with CE_GPU_EINVAL and the key(s) in the
  * text before anything is uploaded.
+ * A fourth: gpu_row_ops = 1 applies ce_gpu_model_admit_row_ops to the loaded
+ * model before gpu_pad_widths and gpu_gemm; a value other than 0 or 1 fails
+ * with CE_GPU_EINVAL and "gpu_row_ops = <value>" in the text.  Beside
+ * gpu_int8_ranges it is accepted and has no effect.
  * Fails with CE_GPU_ENOTSUP for a topology whose whole-utterance result
  * would differ from the reference's chunked one. */
 int ce_gpu_model_load_config(ce_gpu_ctx *ctx, const char *config_path, ce_gpu_model **out);
@@ -434,6 +452,42 @@ int ce_gpu_gemm_mode_from_name(const char *name, int *mode);
  * the quantize entries it belongs right after the load: a session set sizes
  * its caches from the model's widths when it is created. */
 int ce_gpu_model_pad_widths(ce_gpu_ctx *ctx, ce_gpu_model *m);
+
+/* Admits a loaded model's row steps to the matrix-core programs.  A layer
+ * that cannot be a Linear's fused epilogue -- every Normalize and Softmax, a
+ * LogSoftmax that is not the last layer, a fifth post op or a second
+ * BatchNorm behind one Linear, any ReLU / BatchNorm behind one of those
+ * (NormalizeLayer, SoftmaxLayer, LogSoftmaxLayer, ReLULayer, BatchNormLayer:
+ * src/nnet.cc:106-175; the layer loop of Nnet::Propagate, src/nnet.cc:295-307)
+ * -- is a step of its own, and a model with one loads as CE_GPU_GEMM_FP32 and
+ * takes no other mode.  Opt-in: after this call the load-time rule looks at
+ * the Linear layers only, the rule is applied again (a model whose Linears
+ * fit the envelope ends in CE_GPU_GEMM_BF16X6 in the product library),
+ * ce_gpu_model_set_gemm accepts CE_GPU_GEMM_FP32, CE_GPU_GEMM_BF16X6 and
+ * CE_GPU_GEMM_BF16, and ce_gpu_model_pad_widths accepts the model (a row
+ * step keeps its true width: Normalize's D and the sums cover true columns
+ * only, the pad columns stay +0).  CE_GPU_GEMM_BF16X6_PLANES and
+ * CE_GPU_GEMM_F16X3 stay CE_GPU_ENOTSUP for a model that has a row step.
+ *   A row step is a function of one fp32 row with exactly ce_gpu_rowwise's
+ * arithmetic and summation order, so a given fp32 row gives the same bits in
+ * every program, whatever the row count, the leading dimension or latency
+ * mode.  fp32 and bf16x6 run the steps in place on the fp32 block the Linear
+ * before them wrote (in latency mode after its slice reduce; the fused
+ * reduce + finalize is taken only when no row step follows the last Linear).
+ * In CE_GPU_GEMM_BF16 a Linear that row steps follow writes fp32, the steps
+ * run in fp32 and the last of them stores bf16 (round to nearest even) for
+ * the next Linear: a value is still rounded to bf16 exactly once.  An
+ * all-zero row under Normalize gives NaN, as in the reference.
+ *   Sessions of either kind, ce_gpu_model_calibrate (CE_GPU_GEMM_FP32 and
+ * CE_GPU_GEMM_BF16X6; a Linear's range is taken after the row steps before
+ * it), ce_gpu_model_quantize and ce_gpu_model_quantize_static work on an
+ * admitted model as on any other.
+ *   Idempotent.  Returns CE_GPU_OK and changes nothing for a model without a
+ * row step; CE_GPU_EINVAL for an int8 model of either form (the int8
+ * programs run row steps as they are).  Like ce_gpu_model_pad_widths it
+ * belongs right after the load, before pad_widths and set_gemm (the config
+ * key gpu_row_ops = 1 applies it there). */
+int ce_gpu_model_admit_row_ops(ce_gpu_ctx *ctx, ce_gpu_model *m);
 
 /* Each Linear's output width as the net has it (h_true) and as the model
  * runs it (h_padded; equal unless ce_gpu_model_pad_widths changed it), for
