@@ -37,10 +37,10 @@ HOSTFLAGS := -O2 -fPIC -std=c++17 -ffp-contract=off -Iinclude -I$(SRC) -I/opt/ro
 
 KERNELS := $(wildcard $(SRC)/kernels/*.hip)
 HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc \
-           $(SRC)/nnet_programs.cc
+           $(SRC)/nnet_programs.cc $(SRC)/model.cc $(SRC)/weight_images.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
         $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
-HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_i8_kernels.h $(SRC)/nnet_programs.h
+HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_i8_kernels.h $(SRC)/nnet_programs.h $(SRC)/weight_images.h
 
 all: $(LIB) oracle
 
@@ -149,7 +149,14 @@ RANGESASAN := build/bin/ranges_fuzz_asan
 $(RANGESASAN): tests/native/ranges_fuzz.cc $(SRC)/model_io.cc $(SRC)/model_io.h include/catears_gpu.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -std=c++17 -Wall -Iinclude -I$(SRC) -o $@ tests/native/ranges_fuzz.cc $(SRC)/model_io.cc
-sanitize: $(COMPATASAN) $(FUZZASAN) $(RANGESASAN)
+# the weight images' host arithmetic (weight_images.cc alone, no HIP) checked
+# against the formats' definitions and the kernels' documented layouts
+WIMGASAN := build/bin/weight_images_asan
+$(WIMGASAN): tests/native/weight_images_test.cc $(SRC)/weight_images.cc $(SRC)/weight_images.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANFLAGS) -std=c++17 -ffp-contract=off -Wall -Iinclude -I$(SRC) -o $@ tests/native/weight_images_test.cc \
+	    $(SRC)/weight_images.cc
+sanitize: $(COMPATASAN) $(FUZZASAN) $(RANGESASAN) $(WIMGASAN)
 .PHONY: sanitize
 
 host: $(PKLIB) $(PKTEST) $(COMPATTEST)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "catears_gpu.h"
+#include "weight_images.h"  // kX6DirUnits, round_up
 
 namespace catears {
 
@@ -244,7 +245,6 @@ struct GemmLayer {
   int in_left = 0, in_right = 0;
 };
 
-// Same numbering as the ABI's CE_GPU_ROW_* (checked in capi.cc).
 // int8 form of one Linear layer (kernels/nnet_i8.hip), built by
 // ce_gpu_model_quantize.  The A operand is the quantized layer input: either
 // read through the splice offsets (segment width a_din a multiple of the
@@ -269,6 +269,7 @@ struct I8Layer {
   const void *qp = nullptr;
 };
 
+// Same numbering as the ABI's CE_GPU_ROW_* (checked in capi.cc).
 enum RowOpKind : int { kRowRelu, kRowBatchNorm, kRowLogSoftmax, kRowSoftmax, kRowNormalize };
 
 struct RowOp {
@@ -456,6 +457,13 @@ struct ce_gpu_plan {
 
 namespace catears {
 
+// A packed row's word of ce_gpu_plan::d_row_edge: the rows between it and its
+// segment's first and last row, each saturated at 0xffff.
+inline uint32_t row_edge_word(int64_t to_start, int64_t to_end) {
+  const uint32_t dl = (uint32_t)(to_start < 0xffff ? to_start : 0xffff), dr = (uint32_t)(to_end < 0xffff ? to_end : 0xffff);
+  return dl | (dr << 16);
+}
+
 // The program has a row step of its own (a layer that is no Linear's epilogue).
 inline bool has_row_steps(const ce_gpu_model *m) {
   for (const Step &st : m->steps)
@@ -518,7 +526,6 @@ int gemm_k_align();
 // segment); w: n x ldw, plane stride pw (zero padded to kpad); output split
 // (y16, plane stride py) or fp32 (y32).
 int launch_gemm_bf16x6(hipStream_t s, const X6Gemm &a);
-constexpr int kX6DirUnits = 256;  // gemm_bf16x6d_kernel's unit tile
 // Latency mode (kernels/gemm_bf16x6_lat.hip): K split into
 // x6_lat_slices(kpad, n) slices (a function of K and N only), every slice's
 // fp32 partial stored, then summed in slice order by a reduce kernel that

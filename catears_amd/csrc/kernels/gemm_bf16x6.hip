@@ -21,7 +21,7 @@
 //
 // Layout (HBM):
 //   weights  n x ldw bf16, row j = [plane0 | plane1 | plane2], plane stride pw
-//            (= kpad, zero padded), uploaded once (capi.cc split_weights)
+//            (= kpad, zero padded), uploaded once (weight_images.cc bf16_plane_image)
 //   acts     rows x ldx bf16, row r = [plane0 | plane1 | plane2], stride px;
 //            written split by the previous layer's epilogue (or by
 //            splice_pad_split for the first layer)

@@ -88,8 +88,6 @@ static void cover(Layout *all, const Layout &L) {
   all->overflow = all->overflow || L.overflow;
 }
 
-static size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
-
 // ---------------------------------------------------------------- knobs --
 
 // CATEARS_SPLICE_FIRST=0 (experiments library) keeps the gather loader for
@@ -203,7 +201,7 @@ static int max_operand_width(const ce_gpu_model *m, int round) {
   return w;
 }
 
-static size_t last_gemm_step(const ce_gpu_model *m) {
+size_t last_gemm_step(const ce_gpu_model *m) {
   size_t last = 0;
   for (size_t i = 0; i < m->steps.size(); ++i)
     if (m->steps[i].is_gemm) last = i;

@@ -1,4 +1,4 @@
-// nnet_programs.h -- what the entries that run a network (capi.cc,
+// nnet_programs.h -- what the entries that run a network (capi.cc, model.cc,
 // sessions.cc) need of nnet_programs.cc; score_packed_rows and
 // reserve_packed_rows are declared in internal.h.
 #pragma once
@@ -22,6 +22,10 @@ struct CalibTap {
   const uint32_t *row_edge = nullptr;
   int linear = 0;
 };
+
+// The index of the program's last Linear step: the one whose output width is
+// the leading dimension of the program's output.
+size_t last_gemm_step(const ce_gpu_model *m);
 
 // Grows ctx->scratch to `bytes` (the stream is synchronized before a buffer
 // still in use is replaced).

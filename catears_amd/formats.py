@@ -4,7 +4,7 @@ VEC0 / MAT0 (src/vector.cc:267-300, src/matrix.cc:159-191), NN02 nnet with LAY0
 layers (src/nnet.cc:221-293; writer side tool/convert_am.py:26-168) and the
 key = value AM config (src/configuration.cc:14-90, keys of src/am.cc:31-60).
 Host-side plumbing shared by the synthetic-model generator, tests and bench;
-the device loader of the product is the C++ one in csrc/capi.cc.
+the device loader of the product is the C++ one in csrc/model.cc.
 """
 import os
 import struct

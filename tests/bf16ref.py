@@ -18,7 +18,7 @@ import netgen
 
 def rne_bf16(x):
     """float32 -> the nearest bf16 (ties to even), returned as float32.
-    On the uint32 bits, as capi.cc's bf16_rne / v_cvt_pk_bf16_f32."""
+    On the uint32 bits, as weight_images.cc's bf16_rne / v_cvt_pk_bf16_f32."""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32)
     nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
     r = (u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xffff0000)

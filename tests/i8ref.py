@@ -13,7 +13,7 @@ exchanges the left and right contexts.  A wrong rule's parameters are only
 reported, never applied -- the activations stay the reference's -- and exist
 nowhere but here.
 
-paths restates the host's choices per Linear (csrc/capi.cc quantize_weights;
+paths restates the host's choices per Linear (csrc/model.cc quantize_weights;
 csrc/nnet_programs.cc run_steps_i8, run_steps_i8_static; kernels/nnet_i8.hip launch_i8_quantize,
 launch_i8_gemm; kernels/nnet_i8_lat.hip), so the CPU tests can assert that the
 geometries reach every class of them.

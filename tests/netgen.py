@@ -316,7 +316,7 @@ def exact_cases(geom):
 
 
 # ------------------------------------------------ the dispatch rules, read --
-# A restatement of the host-side kernel choice (csrc/capi.cc build_program,
+# A restatement of the host-side kernel choice (csrc/model.cc build_program,
 # csrc/nnet_programs.cc run_steps_*, kernels/gemm_bf16x6.hip launch_gemm_bf16x6 / gemm_bf16x6_kernels.h x6w_fits,
 # kernels/gemm_bf16x6_lat.hip x6_lat_slices, kernels/gemm_f32.hip launch_glds,
 # kernels/rowops.hip launch_finalize), so tests/test_netgen.py can assert

@@ -1,4 +1,4 @@
-"""ce_gpu_model_pad_widths restated on netgen layer lists (csrc/capi.cc), and
+"""ce_gpu_model_pad_widths restated on netgen layer lists (csrc/model.cc), and
 the geometries of tests/test_padnet.py / tests/test_gpu_pad_widths.py.
 
 pad_layers moves a net onto padded widths: every hidden Linear's output width

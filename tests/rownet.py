@@ -152,7 +152,7 @@ def eval_f64(layers, x):
 # ------------------------------------------------------ what the loader does --
 
 def steps(layers):
-    """build_program's step list (csrc/capi.cc): "gemm" per Linear, the kind
+    """build_program's step list (csrc/model.cc): "gemm" per Linear, the kind
     of every layer that becomes a step of its own.  A ReLU / BatchNorm is
     fused while its Linear's chain is open: fewer than 4 post ops, no second
     BatchNorm, no row step yet.  A final LogSoftmax is the finalize."""
