@@ -196,14 +196,21 @@ NNET_GEOMS = ["A", "B", "C", "D", "E", "H", "F4099"]
 def test_exact_nets(torch, G, ctxs, geom, mode):
     """fp32 (splice_pad, the LDS-DMA kernel or pipe2 on the caller's rows),
     bf16x6 and latency (the loaders' gather or splice_pad), the plane program
-    (splice_pad_split), the fp32 fallback program (E, F4099)."""
+    (splice_pad_split), the fp32 fallback program (E, F4099).  The WIDE case
+    of each geometry: what a buffer's layout can break is the loaders'
+    addressing, which does not depend on the operands' planes; the plane
+    recipes (W3, A3, P11) and the binade-shifted forms of netgen.exact_cases
+    are left to tests/test_gpu_gemm_shapes.py."""
     name, layers, x, want = exact_cases(geom)[0]
+    assert name == "wide"
     ctx, model = load(G, ctxs, layers, mode)
     failures = sweep(torch, G, ctx, model, row_cases(x, want, model.left + model.right), f"{geom} {name} {mode}")
     assert not failures, "\n".join(failures[:20])
 
 
 def test_exact_f16x3(torch, G):
+    """B2's WIDE case; the f16x3 plane recipes (F1, FX, FW) are left to
+    tests/test_gpu_gemm_shapes.py."""
     ctx = G.Context(0)
     (name, layers, x, want), = exact_cases("B2")
     model = G.Model(ctx, image=netgen.image(layers)).set_gemm("f16x3")

@@ -72,7 +72,7 @@ def run(torch, G, ctx, model, x, **kw):
 @functools.lru_cache(maxsize=None)
 def exact_cases(geom):
     out = []
-    for name, layers, x in netgen.exact_cases(geom):
+    for name, layers, x in netgen.one_plane_mode_cases(geom):
         want = bf16ref.walk(layers, x, np.float64)
         want.setflags(write=False)
         out.append((name, layers, x, want))

@@ -87,20 +87,18 @@ def first_diff(got, want):
 
 
 @functools.lru_cache(maxsize=None)
-def exact_cases(geom):
+def exact_cases(geom, form="bf16x6"):
     """[(name, layers, x, want)], checked against the budget once."""
     out = []
-    for name, layers, x in netgen.exact_cases(geom):
+    for name, layers, x in netgen.exact_cases(geom, form):
         if "*2^" not in name:
-            netgen.check_exact_budget(layers, x, plane_max=2047 if geom == "B2" else None)
+            netgen.check_exact_budget(layers, x, form)
+            if geom == "B2":
+                netgen.check_exact_budget(layers, x, "f16x3")
         want = netgen.exact(layers, x)
         want.setflags(write=False)
         out.append((name, layers, x, want))
     return out
-
-
-def rows_of(geom):
-    return netgen.ROWS + ((netgen.BIG_ROWS,) if geom in netgen.BIG else ())
 
 
 # ------------------------------------------------------ exact-integer leg --
@@ -108,11 +106,15 @@ def rows_of(geom):
 @pytest.mark.parametrize("mode", list(MODES))
 @pytest.mark.parametrize("geom", EXACT_GEOMS)
 def test_exact_integer_nets(torch, G, ctxs, geom, mode):
+    """Every case of netgen.exact_cases: WIDE, TWO_PLANES, the plane recipes
+    (W3@p, A3, P11@p: every plane product the bf16x6 kernels keep, nonzero at
+    every position of every kernel family -- the matrix and the mutation
+    proofs are in tests/test_netgen.py) and the binade-shifted forms."""
     failures = []
     for name, layers, x, want in exact_cases(geom):
         ctx, model = load(G, ctxs, layers, mode)
         ctx_rows = model.left + model.right
-        for r in rows_of(geom):
+        for r in netgen.case_rows(geom, name):
             got = G.nnet_propagate(ctx, model, dev(torch, x[:r + ctx_rows])).cpu().numpy()
             d = first_diff(got, want[:r])
             if d:
@@ -120,17 +122,35 @@ def test_exact_integer_nets(torch, G, ctxs, geom, mode):
     assert not failures, "\n".join(failures)
 
 
-def test_exact_integer_f16x3(torch, G):
-    """f16x3 drops the a1b1 product: exact only while every Linear's inputs
-    and weights fit one fp16 plane (|v| <= 2047, the B2 recipe); its range is
-    limited, so no binade-shifted form."""
-    ctx = G.Context(0)
-    (name, layers, x, want), = exact_cases("B2")
+F16_CASES = [(g, name) for g in sorted(netgen.GEOMETRIES)
+             for name in (["wide"] if g == "B2" else []) + netgen.recipe_names(g, "f16x3")]
+
+
+@pytest.fixture(scope="module")
+def f16_ctx(torch, G):
+    return G.Context(0)
+
+
+@pytest.mark.parametrize("geom,name", F16_CASES)
+def test_exact_integer_f16x3(torch, G, f16_ctx, geom, name):
+    """f16x3 drops the a1b1 product: exact while, per Linear, one operand
+    fits one fp16 plane (|v| <= 2047) and two planes hold every operand and
+    hidden output (check_exact_budget's f16x3 form).  B2's WIDE net and F1
+    keep every operand in one plane (a0b0 alone); FX puts two-plane
+    activations on one-plane weights at the first and the later Linears
+    (a1b0: the second accumulator, the epilogue's 2^-11 recombination, the
+    split of the hidden outputs), FW@p two-plane weights on one-plane
+    activations (a0b1).  Spliced first and hidden layers, K-tiles of 32 and
+    of 64.  Its range is limited, so no binade-shifted form."""
+    ctx = f16_ctx
+    assert not ctx.overflow()
+    (layers, x, want), = [c[1:] for c in exact_cases(geom, "f16x3") if c[0] == name]
     model = G.Model(ctx, image=netgen.image(layers)).set_gemm("f16x3")
     assert model.gemm == "f16x3"
+    assert netgen.case_rows(geom, name) == netgen.ROWS
     for r in netgen.ROWS:
         got = G.nnet_propagate(ctx, model, dev(torch, x[:r + model.left + model.right])).cpu().numpy()
-        assert first_diff(got, want[:r]) is None, f"rows={r}: {first_diff(got, want[:r])}"
+        assert first_diff(got, want[:r]) is None, f"rows={r} {netgen.f16x3_kernels(layers)}: {first_diff(got, want[:r])}"
     assert not ctx.overflow()
 
 

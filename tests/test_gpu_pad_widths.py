@@ -148,7 +148,8 @@ def test_exact_integer_f16x3(torch, G):
     ctx = G.Context(0)
     layers = netgen.int_net(40, [50, 37], [[0], [0]], [netgen.RB, ("batchnorm",)], netgen.WIDE, seed=4100)
     x = netgen.int_input(layers, netgen.ROWS[-1], 4600)
-    netgen.check_exact_budget(layers, x, plane_max=2047)
+    netgen.check_exact_budget(layers, x, "f16x3")
+    assert all(pairs == {(0, 0)} for pairs in netgen.census(layers, x, "f16x3"))
     want = netgen.exact(layers, x)
     model = padded_model(G, ctx, layers, "f16x3")
     assert model.padded_widths()[1].tolist() == [64, 40]
