@@ -757,4 +757,37 @@ int ce_gpu_debug_rowop_chain(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int r
   return launch_rowop_chain(ctx->stream, ch, d_x, ld, rows, d_out16, ld16, width16);
 }
 
+int ce_gpu_debug_rowop_chain_q(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int rows, int dim, float *d_x, int ld,
+                               const float *const *h_scale, const float *const *h_offset, float scale,
+                               int32_t zero_point, int8_t *d_q, int ldq, int32_t *d_rowsum, int32_t *d_zero) {
+  if (!ctx || n_ops < 0 || n_ops > kRowChainMax || (n_ops > 0 && !h_ops) || rows < 0 || dim <= 0 || ld < dim ||
+      ldq < dim)
+    return fail(CE_GPU_EINVAL, "bad argument");
+  if (!d_x || !d_q || !d_rowsum || !d_zero) return fail(CE_GPU_EINVAL, "NULL argument");
+  if (rows == 0) return CE_GPU_OK;
+  CE_HIP(hipSetDevice(ctx->device));
+  // the parameters as the kernel reads a layer's: a QP in device memory,
+  // written in stream order (an earlier call's launch has read its own)
+  if (!ctx->debug_qp.ptr) CE_TRY(ctx->debug_qp.alloc(256));
+  uint32_t scale_bits;
+  memcpy(&scale_bits, &scale, 4);
+  CE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->debug_qp.ptr), (int)scale_bits, 1, ctx->stream));
+  CE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(static_cast<char *>(ctx->debug_qp.ptr) + 4), zero_point, 1,
+                           ctx->stream));
+  RowChain ch;
+  ch.n = n_ops;
+  ch.dim = dim;
+  for (int q = 0; q < n_ops; ++q) {
+    ch.kind[q] = h_ops[q];
+    ch.scale[q] = h_scale ? h_scale[q] : nullptr;
+    ch.offset[q] = h_offset ? h_offset[q] : nullptr;
+  }
+  return launch_rowop_chain_q(ctx->stream, ch, d_x, ld, rows, dim, d_q, ldq, ctx->debug_qp.ptr, d_rowsum, d_zero);
+}
+
+int ce_gpu_debug_i8_static_launches(int64_t *quantize_passes, int64_t *row_launches, int64_t *row_launches_q) {
+  i8_static_launch_counts(quantize_passes, row_launches, row_launches_q);
+  return CE_GPU_OK;
+}
+
 }  // extern "C"

@@ -360,6 +360,7 @@ struct ce_gpu_ctx {
   catears::DevBuf overflow;    // int: an f16x3 split left the fp16 range (ce_gpu_ctx_overflow)
   catears::DevBuf lat_part;    // latency GEMM: slice partials (grown on demand)
   catears::DevBuf lat_tickets; // latency GEMM fix-up: kX6LatTickets words, zero between launches
+  catears::DevBuf debug_qp;    // ce_gpu_debug_rowop_chain_q: the call's (scale, zero point), set in stream order
   int latency = 0;             // ce_gpu_ctx_set_latency: split-K GEMMs for small batches
   int wide_tiles = 0;          // ce_gpu_ctx_set_wide_tiles: 128 x 128 bf16x6 tiles (all CUs per launch)
   int fbank_mode = 0;          // ce_gpu_ctx_set_fbank: CE_GPU_FBANK_EXACT / _FAST
@@ -613,6 +614,13 @@ int launch_rowop(hipStream_t s, const RowOp &op, float *x, int ldx, int rows);
 // on in x.  ch.n == 0 with out16: the conversion alone.
 int launch_rowop_chain(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, uint16_t *out16 = nullptr,
                        int ld16 = 0, int width16 = 0);
+// The byte form (static int8): the steps of `ch` on `width` == ch.dim columns
+// (ch.n == 0: none), then each row leaves as the shifted bytes of
+// launch_i8_quantize under the device parameters qp (a QP) in q, ldq >= width
+// apart with the bytes behind width zero, its byte sum stored in rowsum[row]
+// and zero[row] cleared.  x is working memory for rows wider than 4096 only.
+int launch_rowop_chain_q(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, int width, int8_t *q, int ldq,
+                         const void *qp, int32_t *rowsum, int32_t *zero);
 int launch_trace_mark(hipStream_t s, int tag);
 int launch_loglik_gather(hipStream_t s, const float *ll, int rows, int ld, int dim, const int32_t *tpm, int n_tid,
                          const int32_t *row, const int32_t *trans, int n, float scale, float *out);

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "../i8_ops.h"
 #include "../internal.h"
 
 namespace catears {
@@ -191,7 +192,14 @@ __global__ __launch_bounds__(256) void rowop_kernel(int kind, float *__restrict_
 // into a sum or written).  OUT = uint16_t: the row leaves as bf16 (round to
 // nearest even, v_cvt_pk_bf16_f32) in another block, `width` >= dim columns
 // of it: the columns behind dim (a padded model's +0 columns) are converted
-// as they are.
+// as they are.  OUT = int8_t (static int8): the row leaves as the next
+// Linear's shifted bytes, qbyte (i8_ops.h: the quantize pass's one definition)
+// under that layer's frozen parameters *qa.qp, columns 0 .. width - 1 (width
+// == dim) of a row of ldo bytes, the bytes behind width written as 0; the
+// lane adds its bytes, the wave's xor tree the lanes' sums (int32: exact in
+// any order), and lane 0 stores qa.rowsum[row] and clears qa.zero[row] -- the
+// quantize pass's contract, no atomics.  The fp32 values that
+// are quantized are the in-place form's bits.
 //   NJ columns per lane: every load of the row is issued (branch-free, on a
 // clamped column) before the first use.  Step q's kind sits in bits 4 q .. of
 // `kinds`; the steps' vectors are picked with static indices (a runtime index
@@ -202,6 +210,12 @@ struct RowChainArgs {
   int kinds, n, dim, width;
 };
 
+// The byte form's extra arguments (unused by the other two).
+struct RowChainQ {
+  const QP *qp;
+  int32_t *rowsum, *zero;
+};
+
 template <class OUT>
 __device__ __forceinline__ void store_row_value(OUT *o, float v) {
   if constexpr (std::is_same<OUT, float>::value)
@@ -210,8 +224,22 @@ __device__ __forceinline__ void store_row_value(OUT *o, float v) {
     *o = __builtin_bit_cast(uint16_t, (__bf16)v);
 }
 
+// The byte form's tail of a row: the pad bytes, the wave's row sum, the word
+// cleared for the GEMM after the next.
+__device__ __forceinline__ void finish_row_bytes(const RowChainQ &qa, int8_t *o, int width, int ldo, int row, int lane,
+                                                 int sum) {
+  for (int c = width + lane; c < ldo; c += 64) o[c] = 0;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  if (lane == 0) {
+    qa.rowsum[row] = sum;
+    qa.zero[row] = 0;
+  }
+}
+
 template <class OUT, int NJ>
-__global__ __launch_bounds__(256) void rowop_chain_kernel(RowChainArgs a, float *x, int ldx, int rows, OUT *out, int ldo) {
+__global__ __launch_bounds__(256) void rowop_chain_kernel(RowChainArgs a, float *x, int ldx, int rows, OUT *out, int ldo,
+                                                          RowChainQ qa) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float *xr = x + (int64_t)row * ldx;
@@ -286,17 +314,32 @@ __global__ __launch_bounds__(256) void rowop_chain_kernel(RowChainArgs a, float 
     }
   }
   OUT *o = out + (int64_t)row * ldo;
+  if constexpr (std::is_same<OUT, int8_t>::value) {
+    // one byte per lane and j: 64 consecutive bytes per store of the wave
+    const QP p = *qa.qp;
+    const float zp = (float)p.zp, rs = qbyte_rscale(p.scale);
+    int sum = 0;
 #pragma unroll
-  for (int j = 0; j < NJ; ++j)
-    if (lane + 64 * j < width) store_row_value(o + lane + 64 * j, v[j]);
+    for (int j = 0; j < NJ; ++j)
+      if (lane + 64 * j < width) {
+        const int b = qbyte(v[j], p.scale, zp, rs);
+        o[lane + 64 * j] = (int8_t)b;
+        sum += b;
+      }
+    finish_row_bytes(qa, o, width, ldo, row, lane, sum);
+  } else {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      if (lane + 64 * j < width) store_row_value(o + lane + 64 * j, v[j]);
+  }
 }
 
 // Rows wider than 64 * kMaxPerLane: the same steps as loops over the fp32
 // row in place (rowop_kernel's own loops: a lane reads back only what it
-// wrote), then the bf16 copy.
+// wrote), then the bf16 or byte copy.
 template <class OUT>
 __global__ __launch_bounds__(256) void rowop_chain_loop_kernel(RowChainArgs a, float *x, int ldx, int rows, OUT *out,
-                                                               int ldo) {
+                                                               int ldo, RowChainQ qa) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   float *xr = x + (int64_t)row * ldx;
@@ -343,23 +386,35 @@ __global__ __launch_bounds__(256) void rowop_chain_loop_kernel(RowChainArgs a, f
         break;
     }
   }
-  if constexpr (!std::is_same<OUT, float>::value) {
+  if constexpr (std::is_same<OUT, int8_t>::value) {
+    int8_t *o = out + (int64_t)row * ldo;
+    const QP p = *qa.qp;
+    const float zp = (float)p.zp, rs = qbyte_rscale(p.scale);
+    int sum = 0;
+    for (int c = lane; c < a.width; c += 64) {
+      const int b = qbyte(xr[c], p.scale, zp, rs);
+      o[c] = (int8_t)b;
+      sum += b;
+    }
+    finish_row_bytes(qa, o, a.width, ldo, row, lane, sum);
+  } else if constexpr (!std::is_same<OUT, float>::value) {
     OUT *o = out + (int64_t)row * ldo;
     for (int c = lane; c < a.width; c += 64) store_row_value(o + c, xr[c]);
   }
 }
 
 template <class OUT>
-int launch_rowop_chain_as(hipStream_t s, const RowChainArgs &a, float *x, int ldx, int rows, OUT *out, int ldo) {
+int launch_rowop_chain_as(hipStream_t s, const RowChainArgs &a, float *x, int ldx, int rows, OUT *out, int ldo,
+                          const RowChainQ &qa = RowChainQ{}) {
   const dim3 grid((rows + 3) / 4), block(256);
   if (a.width <= 64 * 4)
-    hipLaunchKernelGGL((rowop_chain_kernel<OUT, 4>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+    hipLaunchKernelGGL((rowop_chain_kernel<OUT, 4>), grid, block, 0, s, a, x, ldx, rows, out, ldo, qa);
   else if (a.width <= 64 * 16)
-    hipLaunchKernelGGL((rowop_chain_kernel<OUT, 16>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+    hipLaunchKernelGGL((rowop_chain_kernel<OUT, 16>), grid, block, 0, s, a, x, ldx, rows, out, ldo, qa);
   else if (a.width <= 64 * kMaxPerLane)
-    hipLaunchKernelGGL((rowop_chain_kernel<OUT, kMaxPerLane>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+    hipLaunchKernelGGL((rowop_chain_kernel<OUT, kMaxPerLane>), grid, block, 0, s, a, x, ldx, rows, out, ldo, qa);
   else
-    hipLaunchKernelGGL((rowop_chain_loop_kernel<OUT>), grid, block, 0, s, a, x, ldx, rows, out, ldo);
+    hipLaunchKernelGGL((rowop_chain_loop_kernel<OUT>), grid, block, 0, s, a, x, ldx, rows, out, ldo, qa);
   CE_HIP(hipGetLastError());
   return CE_GPU_OK;
 }
@@ -606,13 +661,8 @@ int launch_rowop(hipStream_t s, const RowOp &op, float *x, int ldx, int rows) {
   return launch_rowop_raw(s, op.kind, op.dim, op.scale.as<float>(), op.offset.as<float>(), x, ldx, rows);
 }
 
-int launch_rowop_chain(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, uint16_t *out16, int ld16,
-                       int width16) {
-  if (ch.n < 0 || ch.n > kRowChainMax) return fail(CE_GPU_EINVAL, "rowop_chain: 0..4 steps per launch");
-  const int width = out16 ? width16 : ch.dim;
-  if (ch.dim < 0 || ldx < width || (out16 && (width < ch.dim || ld16 < width)))
-    return fail(CE_GPU_EINVAL, "rowop_chain: a row does not hold its width");
-  if (rows <= 0 || width == 0 || (ch.n == 0 && !out16)) return CE_GPU_OK;
+// The kernel's form of `ch` on rows of `width` columns.
+static int chain_args(const RowChain &ch, int width, RowChainArgs *out) {
   RowChainArgs a = {};
   a.n = ch.dim > 0 ? ch.n : 0;
   a.dim = ch.dim;
@@ -625,8 +675,33 @@ int launch_rowop_chain(hipStream_t s, const RowChain &ch, float *x, int ldx, int
     a.scale[q] = ch.scale[q];
     a.offset[q] = ch.offset[q];
   }
+  *out = a;
+  return CE_GPU_OK;
+}
+
+int launch_rowop_chain(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, uint16_t *out16, int ld16,
+                       int width16) {
+  if (ch.n < 0 || ch.n > kRowChainMax) return fail(CE_GPU_EINVAL, "rowop_chain: 0..4 steps per launch");
+  const int width = out16 ? width16 : ch.dim;
+  if (ch.dim < 0 || ldx < width || (out16 && (width < ch.dim || ld16 < width)))
+    return fail(CE_GPU_EINVAL, "rowop_chain: a row does not hold its width");
+  if (rows <= 0 || width == 0 || (ch.n == 0 && !out16)) return CE_GPU_OK;
+  RowChainArgs a;
+  CE_TRY(chain_args(ch, width, &a));
   if (out16) return launch_rowop_chain_as<uint16_t>(s, a, x, ldx, rows, out16, ld16);
   return launch_rowop_chain_as<float>(s, a, x, ldx, rows, x, ldx);
+}
+
+int launch_rowop_chain_q(hipStream_t s, const RowChain &ch, float *x, int ldx, int rows, int width, int8_t *q, int ldq,
+                         const void *qp, int32_t *rowsum, int32_t *zero) {
+  if (ch.n < 0 || ch.n > kRowChainMax) return fail(CE_GPU_EINVAL, "rowop_chain: 0..4 steps per launch");
+  if (ch.dim <= 0 || width != ch.dim || ldx < width || ldq < width)
+    return fail(CE_GPU_EINVAL, "rowop_chain: a row of bytes holds the steps' width, no more and no less");
+  if (!x || !q || !qp || !rowsum || !zero) return fail(CE_GPU_EINVAL, "rowop_chain: NULL argument");
+  if (rows <= 0) return CE_GPU_OK;
+  RowChainArgs a;
+  CE_TRY(chain_args(ch, width, &a));
+  return launch_rowop_chain_as<int8_t>(s, a, x, ldx, rows, q, ldq, RowChainQ{static_cast<const QP *>(qp), rowsum, zero});
 }
 
 namespace {

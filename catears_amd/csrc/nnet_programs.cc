@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -212,9 +213,20 @@ size_t last_gemm_step(const ce_gpu_model *m) {
 // the Linear before them wrote: one launch_rowop_chain per kRowChainMax
 // steps.  With out16 the last launch leaves the rows as bf16 there instead,
 // width16 columns of them (the plain bf16 program's hand-over to the next
-// Linear).  *si ends on the next GEMM step, or behind the last step.
+// Linear).  With bytes the last launch leaves them as the next Linear's
+// shifted bytes and row sums instead (the static int8 program's hand-over:
+// launch_rowop_chain_q).  *si ends on the next GEMM step, or behind the last
+// step; *launches (optional) grows by the launches made.
+struct RowBytes {
+  int8_t *q;
+  int ldq;
+  const void *qp;
+  int32_t *rowsum, *zero;
+};
+
 static int run_row_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, size_t *si, float *x, int ldx, int rows,
-                         uint16_t *out16 = nullptr, int ld16 = 0, int width16 = 0) {
+                         uint16_t *out16 = nullptr, int ld16 = 0, int width16 = 0, const RowBytes *bytes = nullptr,
+                         int *launches = nullptr) {
   size_t end = *si;
   while (end < m->steps.size() && !m->steps[end].is_gemm) ++end;
   while (*si < end) {
@@ -227,7 +239,17 @@ static int run_row_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, size_t *si, flo
       ch.offset[ch.n] = op.offset.as<float>();
     }
     const bool store16 = out16 && *si == end;
-    CE_TRY(launch_rowop_chain(ctx->stream, ch, x, ldx, rows, store16 ? out16 : nullptr, ld16, width16));
+    if (bytes && *si == end) {
+      // the next Linear's quantize pass as well, and timed as one: a
+      // profiled call counts a CE_GPU_PROF_QUANT launch per Linear whose
+      // bytes no GEMM epilogue wrote, whichever kernel wrote them
+      ProfScope prof(ctx, CE_GPU_PROF_QUANT);
+      CE_TRY(launch_rowop_chain_q(ctx->stream, ch, x, ldx, rows, ch.dim, bytes->q, bytes->ldq, bytes->qp, bytes->rowsum,
+                                  bytes->zero));
+    } else {
+      CE_TRY(launch_rowop_chain(ctx->stream, ch, x, ldx, rows, store16 ? out16 : nullptr, ld16, width16));
+    }
+    if (launches) ++*launches;
     ctx->chain_end = nullptr;  // an untimed launch breaks a ProfChain
   }
   return CE_GPU_OK;
@@ -691,8 +713,12 @@ static int run_steps_i8(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, 
       cur ^= 1;
       first = false;
     } else {
+      // the run of row steps that starts here, one launch per chain in place
+      // (launch_rowop's bits): this program's parameters are reduced over the
+      // block behind them, so no byte store here
       fused_parts = 0;
-      CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
+      CE_TRY(run_row_steps(ctx, m, &si, const_cast<float *>(x), ldx, rows));
+      --si;  // the loop steps on to the Linear behind the run
     }
   }
   *y = x;
@@ -704,7 +730,10 @@ static int run_steps_i8(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, 
 // buffers (a GEMM with the requantize epilogue reads one and writes the
 // other) and three row-sum buffers (read / added into / cleared for the next
 // launch); in latency mode the slice partials of the largest layer the slice
-// rule gives the split-K pair at this row count.
+// rule gives the split-K pair at this row count.  Row steps that store bytes
+// need nothing more: they read an fp32 block (rows x max_width) and write an
+// operand buffer (rows x i8_max_ldq) and two row-sum buffers, as the quantize
+// pass they replace does.
 static Layout layout_i8_static(const ce_gpu_model *m, int rows, bool latency) {
   Layout L;
   L.blk = (size_t)rows * m->max_width;
@@ -730,6 +759,36 @@ static Layout layout_i8_static(const ce_gpu_model *m, int rows, bool latency) {
 // quantize pass with the frozen parameters.  CATEARS_I8_FUSED=0 (experiments
 // library, read per call: tools/i8_static.py) keeps the quantize pass
 // everywhere.
+//   A run of row steps between two Linears goes through the chain kernel; where
+// i8_rows_can_quantize holds, its last launch plays the quantize pass's role
+// for the Linear behind it (launch_rowop_chain_q: that layer's bytes into
+// xq[qc], their sums into rs[rc], rs[rc + 1] cleared; no rotation), and that
+// Linear takes the bytes as it takes a requantizing GEMM's.
+static bool i8_fused_env() { return CE_KNOB("CATEARS_I8_FUSED", 1) != 0; }
+
+// true when the run of row steps that starts at step `first_row_step` can hand
+// the Linear behind it its bytes: there is one, it reads the plain row
+// (in_width bytes, ldq = in_width: not spliced), the steps work on that width,
+// and the fused forms are on.  A function of the model alone: a row's bits do
+// not depend on it, and no row count was measured slower.
+static bool i8_rows_can_quantize(const ce_gpu_model *m, size_t first_row_step) {
+  size_t end = first_row_step;
+  while (end < m->steps.size() && !m->steps[end].is_gemm) ++end;
+  if (end == first_row_step || end == m->steps.size() || !i8_fused_env()) return false;
+  const I8Layer &N = m->steps[end].i8;
+  for (size_t i = first_row_step; i < end; ++i)
+    if (m->steps[i].row.dim != N.in_width) return false;
+  return !N.spliced && N.qp != nullptr;
+}
+
+static std::atomic<int64_t> g_i8s_quantize{0}, g_i8s_row{0}, g_i8s_row_q{0};
+
+void i8_static_launch_counts(int64_t *quantize_passes, int64_t *row_launches, int64_t *row_launches_q) {
+  if (quantize_passes) *quantize_passes = g_i8s_quantize.load(std::memory_order_relaxed);
+  if (row_launches) *row_launches = g_i8s_row.load(std::memory_order_relaxed);
+  if (row_launches_q) *row_launches_q = g_i8s_row_q.load(std::memory_order_relaxed);
+}
+
 static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, int rows,
                                const int *row_map, const float **y, int *ldy, const IncrChunk *inc = nullptr) {
   const Layout lay = layout_i8_static(m, rows, ctx->latency != 0);
@@ -739,21 +798,34 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
   int8_t *xq[2] = {reinterpret_cast<int8_t *>(base), reinterpret_cast<int8_t *>(base + lay.xq_stride)};
   int32_t *rs[3];
   for (int i = 0; i < 3; ++i) rs[i] = reinterpret_cast<int32_t *>(base + lay.rowsum + i * lay.rowsum_stride);
-  const bool fused_ok = CE_KNOB("CATEARS_I8_FUSED", 1) != 0;
+  const bool fused_ok = i8_fused_env();
   int cur = 0, qc = 0, rc = 0, linear = 0;
-  bool first = true, have_bytes = false;  // have_bytes: the previous GEMM wrote xq[qc] / rs[rc]
+  // have_bytes: the previous GEMM, or the row steps behind it, wrote xq[qc] / rs[rc]
+  bool first = true, have_bytes = false;
   for (size_t si = 0; si < m->steps.size(); ++si) {
     const Step &st = m->steps[si];
     if (!st.is_gemm) {
-      CE_TRY(launch_rowop(ctx->stream, st.row, const_cast<float *>(x), ldx, rows));
+      // the run of row steps that starts here (x: the fp32 rows the Linear
+      // before them wrote)
+      have_bytes = i8_rows_can_quantize(m, si);
+      size_t end = si;
+      while (end < m->steps.size() && !m->steps[end].is_gemm) ++end;
+      RowBytes rb = {};
+      if (have_bytes) rb = RowBytes{xq[qc], m->steps[end].i8.in_width, m->steps[end].i8.qp, rs[rc], rs[(rc + 1) % 3]};
+      int launches = 0;
+      CE_TRY(run_row_steps(ctx, m, &si, const_cast<float *>(x), ldx, rows, nullptr, 0, 0, have_bytes ? &rb : nullptr,
+                           &launches));
+      g_i8s_row.fetch_add(launches, std::memory_order_relaxed);
+      if (have_bytes) g_i8s_row_q.fetch_add(1, std::memory_order_relaxed);
+      --si;  // the loop steps on to the Linear behind the run
       continue;
     }
     const I8Layer &L = st.i8;
     const int ldq = L.spliced ? L.kpad : L.in_width;
     // an incremental chunk: the cached context joins the layer's input in the
     // form it has here -- fp32 rows ahead of the quantize pass, or the bytes
-    // and row sums the previous GEMM wrote -- and whichever launch reads that
-    // input through the splice offsets reads it causally
+    // and row sums the previous GEMM or its row steps wrote -- and whichever
+    // launch reads that input through the splice offsets reads it causally
     int off[8];
     layer_offsets(st.gemm, inc, off);
     if (!have_bytes) {
@@ -763,6 +835,7 @@ static int run_steps_i8_static(ce_gpu_ctx *ctx, const ce_gpu_model *m, const flo
       CE_TRY(launch_i8_quantize(ctx->stream, x, ldx, rows, L.in_width, first ? row_map : nullptr,
                                 L.spliced ? st.gemm.nseg : 1, L.spliced ? off : zero, L.qp, xq[qc], ldq, rs[rc],
                                 rs[(rc + 1) % 3]));
+      g_i8s_quantize.fetch_add(1, std::memory_order_relaxed);
     } else {
       CE_TRY(exchange_input(ctx, inc, linear, xq[qc], (size_t)L.in_width, (size_t)ldq, rs[rc]));
     }

@@ -39,6 +39,12 @@ int run_steps(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *x, int ldx, i
               const uint32_t *row_edge, const float **y, int *ldy, LatTail *tail = nullptr, CalibTap *tap = nullptr,
               const IncrChunk *inc = nullptr);
 
+// What the static int8 program has enqueued in this process, counted on the
+// host (ce_gpu_debug_i8_static_launches): quantize passes, row-step launches
+// (one per chain of up to kRowChainMax steps), and those of them that stored
+// the next Linear's bytes.
+void i8_static_launch_counts(int64_t *quantize_passes, int64_t *row_launches, int64_t *row_launches_q);
+
 // The latency GEMM may defer its last layer's reduce into the finalize only
 // when the fused finalize can write the caller's output: it stores 16-byte
 // row chunks (launch_lat_finalize), so out and the log prior must be 16-byte

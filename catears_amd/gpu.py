@@ -42,6 +42,7 @@ ABI = [
     "ce_gpu_sessions_create_ex", "ce_gpu_sessions_stats",
     "ce_gpu_model_pad_widths", "ce_gpu_model_padded_widths",
     "ce_gpu_model_admit_row_ops", "ce_gpu_debug_rowop_chain",
+    "ce_gpu_debug_rowop_chain_q", "ce_gpu_debug_i8_static_launches",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -138,6 +139,9 @@ def lib():
         "ce_gpu_model_admit_row_ops": (ci, [vp, vp]),
         "ce_gpu_debug_rowop_chain": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci]),
         "ce_gpu_model_padded_widths": (ci, [vp, vp, vp, ci, pi]),
+        "ce_gpu_debug_rowop_chain_q": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, ctypes.c_float, ctypes.c_int32, vp, ci,
+                                            vp, vp]),
+        "ce_gpu_debug_i8_static_launches": (ci, [pi64, pi64, pi64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -545,6 +549,15 @@ def debug_i8_latency_launches():
     return n.value
 
 
+def debug_i8_static_launches():
+    """ce_gpu_debug_i8_static_launches: (quantize passes, row-step launches,
+    row-step launches that stored the next Linear's bytes) the static int8
+    program has enqueued in this process so far."""
+    q, r, rq = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    check(lib().ce_gpu_debug_i8_static_launches(ctypes.byref(q), ctypes.byref(r), ctypes.byref(rq)))
+    return q.value, r.value, rq.value
+
+
 class Sessions:
     """ce_gpu_sessions: `n_slots` live audio streams scored incrementally,
     their state (sample tail, CMVN sums and window, nnet context) on the
@@ -835,6 +848,23 @@ def rowop_chain(ctx, ops, x, dim=None, vectors=None, out16=None):
     check(lib().ce_gpu_debug_rowop_chain(ctx.h, n, kinds, x.shape[0], dim, _ptr_rows(x), x.stride(0), sc, of, o16,
                                          ld16, w16))
     return x if out16 is None else out16
+
+
+def debug_rowop_chain_q(ctx, ops, x, scale, zero_point, q, rowsum, zero, vectors=None):
+    """ce_gpu_debug_rowop_chain_q: the row ops `ops` (ROW_OPS names, at most
+    4; none: a pure quantize) on the rows of x, which then leave as the next
+    Linear's shifted bytes under (scale, zero_point) in q (an int8 device
+    tensor of x's rows, at least x's columns wide: the columns behind are
+    written as 0), their sums in rowsum[r] with zero[r] cleared (int32 device
+    vectors).  Returns q."""
+    n = len(ops)
+    kinds = (ctypes.c_int * max(n, 1))(*[ROW_OPS[o] for o in ops])
+    sc = (ctypes.c_void_p * max(n, 1))(*[_ptr(vectors[i][0]) if vectors and vectors[i] else None for i in range(n)])
+    of = (ctypes.c_void_p * max(n, 1))(*[_ptr(vectors[i][1]) if vectors and vectors[i] else None for i in range(n)])
+    check(lib().ce_gpu_debug_rowop_chain_q(ctx.h, n, kinds, x.shape[0], x.shape[1], _ptr_rows(x), x.stride(0), sc, of,
+                                           float(scale), int(zero_point), _ptr_rows(q), q.stride(0), _ptr(rowsum),
+                                           _ptr(zero)))
+    return q
 
 
 def quantize(ctx, x, q=None):

@@ -84,7 +84,9 @@ const char *ce_gpu_last_error(void);
  * re-layout onto padded widths (ce_gpu_model_pad_widths,
  * ce_gpu_model_padded_widths, the config key gpu_pad_widths), and so do the
  * row steps in the matrix-core programs (ce_gpu_model_admit_row_ops,
- * ce_gpu_debug_rowop_chain, the config key gpu_row_ops). */
+ * ce_gpu_debug_rowop_chain, the config key gpu_row_ops), and so do the row
+ * steps of a static int8 model that write the next layer's bytes
+ * (ce_gpu_debug_rowop_chain_q, ce_gpu_debug_i8_static_launches). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -189,7 +191,8 @@ int ce_gpu_ctx_set_fbank(ce_gpu_ctx *ctx, int mode);
 #define CE_GPU_PROF_FBANK 2
 #define CE_GPU_PROF_CMVN 3
 #define CE_GPU_PROF_FINALIZE 4
-#define CE_GPU_PROF_QUANT 5 /* int8 path: per-layer min/max + quantize passes */
+#define CE_GPU_PROF_QUANT 5 /* int8 path: per-layer min/max + quantize passes (static int8: also a
+                               row-step launch that writes the next Linear's bytes in a pass's place) */
 #define CE_GPU_PROF_CLASSES 6
 int ce_gpu_ctx_profile(ce_gpu_ctx *ctx, int enable);
 /* Restrict the timing to the classes whose bit (1 << class) is set in
@@ -239,6 +242,27 @@ int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
 int ce_gpu_debug_rowop_chain(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int rows, int dim, float *d_x, int ld,
                              const float *const *h_scale, const float *const *h_offset, uint16_t *d_out16, int ld16,
                              int width16);
+/* The same launch in the form a static int8 model's row steps end on
+ * (ce_gpu_model_quantize_static): the n_ops <= 4 row ops (0: none, a pure
+ * quantize) on `rows` rows of `dim` columns of d_x, then every row leaves as
+ * the next Linear's input bytes under (scale, zero_point) -- Quantize of one
+ * element (src/matrix.cc:378-386) less 128, the bytes of the model's quantize
+ * pass -- in d_q, leading dimension ldq >= dim, the bytes [dim, ldq) of a row
+ * written as 0; d_rowsum[r] receives row r's sum of those bytes and
+ * d_zero[r] is cleared, for r < rows.  d_x is left as it is for dim <= 4096
+ * and is working memory beyond.  The parameters travel by value (the entry
+ * keeps a device copy of its own).  CE_GPU_EINVAL for n_ops > 4, dim <= 0,
+ * ld < dim, ldq < dim or a NULL pointer.  Enqueues on the context's stream.
+ * Measurement plumbing as above. */
+int ce_gpu_debug_rowop_chain_q(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int rows, int dim, float *d_x, int ld,
+                               const float *const *h_scale, const float *const *h_offset, float scale,
+                               int32_t zero_point, int8_t *d_q, int ldq, int32_t *d_rowsum, int32_t *d_zero);
+/* Process-wide counts of what the static int8 program has enqueued (counted
+ * on the host): quantize passes, row-step launches (one per run of up to four
+ * row steps), and those of them that stored the next Linear's bytes in place
+ * of a quantize pass.  Shows which hand-over a model's layers took.  Any
+ * pointer may be NULL.  Measurement plumbing as above. */
+int ce_gpu_debug_i8_static_launches(int64_t *quantize_passes, int64_t *row_launches, int64_t *row_launches_q);
 
 /* -------------------------------------------------------------- model --- */
 

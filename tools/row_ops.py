@@ -2,6 +2,7 @@
 on one MI355X: the TDNN-S shape with every BatchNorm replaced by Normalize
 (the relu-renorm TDNN), one JSON object on stdout.
    python tools/row_ops.py [calls]
+   python tools/row_ops.py --static-int8 [calls]     the same net in static int8, see static_int8()
 
 Legs, on one context, in A B B A order per row count (4072 and 70):
   A  the model as loaded: fp32 mode, the only one it takes;
@@ -141,5 +142,108 @@ def row_kernel(ctx, res, calls, rows=4072, dim=1024):
               file=sys.stderr, flush=True)
 
 
+def static_int8(calls=100):
+    """--static-int8: the same net calibrated and switched to static int8
+    (ce_gpu_model_quantize_static), whose row steps write the next Linear's
+    bytes.  One JSON object: per leg -- 70 rows, 70 rows with the context's
+    latency mode on, 4072 rows -- the p50 / p10 / p90 of the event-bracketed
+    device time of one ce_gpu_nnet_propagate and a checksum of its rows, and
+    what the program enqueued per call (ce_gpu_debug_i8_static_launches, where
+    the library has it).  One process times one library (CATEARS_HIP_LIB): run
+    the baseline library and this one as processes in A B B A order.  With
+    the experiments library CATEARS_I8_FUSED=0 is the unfused program (the
+    chain in place, then the quantize pass).
+    Then the row kernel alone, A B B A in this process: ReLU + Normalize on
+    4072 x 1024 ending in the byte store, against the chain in place followed
+    by a quantize-only launch of the same kernel (no entry runs the model's
+    quantize pass on caller buffers), and that launch alone."""
+    import hashlib
+    spec = synth.MODELS["tdnn-s"]
+    hidden, pdfs = spec["hidden"], spec["pdfs"]
+    layers, left, right, prior = synth.tdnn_layers(hidden, pdfs)
+    layers = [{"kind": "normalize"} if L["kind"] == "batchnorm" else L for L in layers]
+    image = formats.nnet_bytes(layers, left, right)
+    ctx = gpu.Context(0)
+    model = gpu.Model(ctx, image=image, prior=prior)
+    cal = [synth.pcm(2900 + i, 48000) for i in range(4)]
+    plan = gpu.Plan(ctx, [len(w) for w in cal], model)
+    ranges = model.calibrate(ctx, plan, gpu.fbank(ctx, plan, torch.from_numpy(np.concatenate(cal)).cuda()))
+    model.quantize_static(ctx, ranges)
+    counts = getattr(gpu, "debug_i8_static_launches", None)
+    if counts is not None and not hasattr(gpu.lib(), "ce_gpu_debug_i8_static_launches"):
+        counts = None
+    res = {"version": gpu.lib().ce_gpu_version().decode(), "device": torch.cuda.get_device_name(0), "calls": calls,
+           "library": os.path.relpath(gpu.LIB_PATH), "CATEARS_I8_FUSED": os.environ.get("CATEARS_I8_FUSED"),
+           "model": f"tdnn-s shape, hidden {hidden}, {pdfs} pdfs, every BatchNorm replaced by Normalize, static int8",
+           "timing": {}, "row_kernel": {}}
+    for rows, lat in ((70, False), (70, True), (4072, False)):
+        wave = synth.pcm(3950 + rows, 160 * (rows - 1) + 400)
+        p = gpu.Plan(ctx, [len(wave)])
+        x = gpu.fbank(ctx, p, torch.from_numpy(wave).cuda())
+        assert x.shape[0] == rows
+        ctx.set_latency(lat)
+        rec = time_leg(ctx, model, x, calls)
+        if counts is not None:
+            before = counts()
+            gpu.nnet_propagate(ctx, model, x)
+            rec["quantize_passes, row_launches, row_launches_q"] = [a - b for a, b in zip(counts(), before)]
+        out = gpu.nnet_propagate(ctx, model, x).cpu().numpy()
+        ctx.set_latency(False)
+        rec["rows_sha1"] = hashlib.sha1(out.tobytes()).hexdigest()[:16]
+        rec["finite"] = bool(np.isfinite(out).all())
+        name = f"static int8{' + latency' if lat else ''}/{rows}"
+        res["timing"][name] = rec
+        print(f"{name:28s}: p50 {rec['p50_us']:7.1f} us [{rec['p10_us']:.1f}, {rec['p90_us']:.1f}] "
+              f"back to back {rec['back_to_back_us']:7.1f} us", file=sys.stderr, flush=True)
+    if hasattr(gpu.lib(), "ce_gpu_debug_rowop_chain_q") and hasattr(gpu, "debug_rowop_chain_q"):
+        row_kernel_q(ctx, res, calls)
+    print(json.dumps(res))
+
+
+def row_kernel_q(ctx, res, calls, rows=4072, dim=1024):
+    x0 = torch.from_numpy(np.random.default_rng(7).normal(0, 2, size=(rows, dim)).astype(np.float32)).cuda()
+    x = x0.clone()
+    q = [torch.empty((rows, dim), dtype=torch.int8, device="cuda") for _ in range(2)]
+    rs = [torch.empty((rows,), dtype=torch.int32, device="cuda") for _ in range(2)]
+    zero = torch.empty((rows,), dtype=torch.int32, device="cuda")
+    s, z = gpu.quant_params_from_range(-4.0, 4.0)
+    ops = ("relu", "normalize")
+
+    def fused():
+        gpu.debug_rowop_chain_q(ctx, ops, x0, s, z, q[0], rs[0], zero)
+
+    def quantize_only():
+        gpu.debug_rowop_chain_q(ctx, (), x, s, z, q[1], rs[1], zero)
+
+    def in_place():
+        gpu.rowop_chain(ctx, ops, x)
+
+    def two():
+        in_place()
+        quantize_only()
+
+    fused()
+    two()
+    res["row_kernel"]["same_bits"] = bool(torch.equal(q[0], q[1]) and torch.equal(rs[0], rs[1]))
+    legs = {"chain in place + quantize-only launch": two, "chain -> bytes": fused, "chain in place": in_place,
+            "quantize-only launch": quantize_only}
+    order = ["chain in place + quantize-only launch", "chain -> bytes", "chain -> bytes",
+             "chain in place + quantize-only launch", "chain in place", "quantize-only launch"]
+    for run, name in enumerate(order):
+        x.copy_(x0)
+        for _ in range(20):
+            legs[name]()
+        us = per_call_us(legs[name], calls)
+        rec = {"p50_us": round(float(np.percentile(us, 50)), 1), "p10_us": round(float(np.percentile(us, 10)), 1),
+               "p90_us": round(float(np.percentile(us, 90)), 1)}
+        res["row_kernel"][f"{name}/{rows}x{dim}/run{run}"] = rec
+        print(f"{name:40s} {rows} x {dim}: p50 {rec['p50_us']:7.1f} us [{rec['p10_us']:.1f}, {rec['p90_us']:.1f}]",
+              file=sys.stderr, flush=True)
+
+
 if __name__ == "__main__":
-    main(*[int(v) for v in sys.argv[1:2]])
+    nums = [int(v) for v in sys.argv[1:] if not v.startswith("--")][:1]
+    if "--static-int8" in sys.argv[1:]:
+        static_int8(*nums)
+    else:
+        main(*nums)

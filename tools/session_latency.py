@@ -15,6 +15,9 @@ reported are the median and the 10th / 90th percentile over all timed ticks.
 Both legs compute the same rows (checked once per N, bit for bit).
 
   python tools/session_latency.py [ticks] [rounds]      -> JSON lines
+  python tools/session_latency.py --static-int8 --renorm [ticks] [rounds] [--slots N] [--tick-ms T]
+      the relu-renorm model in static int8, incremental and plain sets, see
+      incremental()
   python tools/session_latency.py --static-int8 [ticks] [rounds]
       the 64-stream push only: the bf16x6 latency-mode model beside a static
       int8 model (ce_gpu_model_quantize_static) on a throughput context and
@@ -196,7 +199,18 @@ def static_int8(ticks=100, rounds=3, n=64):
         sess.close()
 
 
-def incremental(ticks=100, rounds=3, n=64, tick_ms=100):
+def renorm_image():
+    """The TDNN-S shape with every BatchNorm replaced by Normalize (the
+    relu-renorm TDNN of tools/row_ops.py): (NN02 image, prior)."""
+    from catears_amd import formats
+    spec = synth.MODELS["tdnn-s"]
+    layers, left, right, prior = synth.tdnn_layers(spec["hidden"], spec["pdfs"])
+    layers = [{"kind": "normalize"} if L["kind"] == "batchnorm" else L for L in layers]
+    return formats.nnet_bytes(layers, left, right), prior
+
+
+def incremental(ticks=100, rounds=3, n=64, tick_ms=100, forms=("static_int8_latency", "bf16", "bf16x6_latency"),
+                renorm=False):
     """N running streams, tick_ms of audio per slot and push, no CMVN: an
     incremental set and a plain (flags = 0) set of the same model on two
     contexts, in alternating blocks of `ticks` pushes, for static int8 and
@@ -204,11 +218,16 @@ def incremental(ticks=100, rounds=3, n=64, tick_ms=100):
     already on the device (the same buffer every tick: 13 MB a tick at 2048
     slots would otherwise be most of what is timed); a host clock brackets
     push + synchronise.  Packed rows per push from ce_gpu_sessions_stats; the
-    last tick's rows of the two sets are compared bit for bit."""
+    last tick's rows of the two sets are compared bit for bit.
+    renorm (--static-int8 --renorm): the relu-renorm model, whose row steps
+    write the next layer's bytes, in the static int8 forms only -- latency
+    mode on and off; time one library per process (CATEARS_HIP_LIB)."""
     mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
     conf = synth.write_model(mdir, "tdnn-s")
+    image, prior = renorm_image() if renorm else (None, None)
     chunk = 16 * tick_ms
-    print(json.dumps({"device": torch.cuda.get_device_name(0), "model": "tdnn-s", "slots": n, "tick_ms": tick_ms,
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "model": "tdnn-s renorm" if renorm else "tdnn-s",
+                      "library": os.path.relpath(gpu.LIB_PATH), "slots": n, "tick_ms": tick_ms,
                       "ticks": ticks, "rounds": rounds, "legs": ["incremental", "plain"],
                       "version": gpu.lib().ce_gpu_version().decode()}), flush=True)
     cal = [synth.pcm(2900 + i, 48000) for i in range(4)]
@@ -216,16 +235,16 @@ def incremental(ticks=100, rounds=3, n=64, tick_ms=100):
     lead = torch.from_numpy(np.concatenate([np.roll(base[s % 8], 5 * s)[:4000] for s in range(n)])).cuda()
     tick = torch.from_numpy(np.concatenate([np.roll(base[s % 8], 5 * s)[4000:] for s in range(n)])).cuda()
     slots = list(range(n))
-    for form in ("static_int8_latency", "bf16", "bf16x6_latency"):
+    for form in forms:
         legs = []
         for inc in (True, False):
             ctx = gpu.Context(0)
-            model = gpu.Model(ctx, conf)
-            if form != "bf16":
+            model = gpu.Model(ctx, image=image, prior=prior) if renorm else gpu.Model(ctx, conf)
+            if form not in ("bf16", "static_int8"):
                 ctx.set_latency(True)
             if form == "bf16":
                 model.set_gemm("bf16")
-            if form == "static_int8_latency":
+            if form in ("static_int8_latency", "static_int8"):
                 plan = gpu.Plan(ctx, [len(w) for w in cal], model)
                 model.quantize_static(ctx, model.calibrate(
                     ctx, plan, gpu.fbank(ctx, plan, torch.from_numpy(np.concatenate(cal)).cuda())))
@@ -275,7 +294,10 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     valued = {i + 1 for i, v in enumerate(argv) if v in ("--slots", "--tick-ms")}
     nums = [int(v) for i, v in enumerate(argv) if not v.startswith("--") and i not in valued][:2]
-    if "--incremental" in argv:
+    if "--static-int8" in argv and "--renorm" in argv:
+        incremental(*(nums + [100, 3][len(nums):]), n=flag("--slots", 64), tick_ms=flag("--tick-ms", 100),
+                    forms=("static_int8_latency", "static_int8"), renorm=True)
+    elif "--incremental" in argv:
         incremental(*(nums + [100, 3][len(nums):]), n=flag("--slots", 64), tick_ms=flag("--tick-ms", 100))
     elif "--static-int8" in sys.argv[1:]:
         static_int8(*nums)
