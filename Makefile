@@ -40,7 +40,7 @@ HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc
            $(SRC)/nnet_programs.cc $(SRC)/model.cc $(SRC)/weight_images.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
         $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
-HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_i8_kernels.h $(SRC)/nnet_programs.h $(SRC)/weight_images.h
+HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/gemm_bf16_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_i8_kernels.h $(SRC)/nnet_programs.h $(SRC)/weight_images.h
 
 all: $(LIB) oracle
 
@@ -118,6 +118,13 @@ $(PKTEST): tests/native/pk_dropin.cc $(PKLIB) $(PKHDRS)
 	$(CXX) $(PKFLAGS) -rdynamic -o $@ $< -Lcatears_amd/lib -lcatears_pk -lcatears_hip -L/opt/rocm/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
+# pk_dropin's `am` mode with a report of the library's latency-GEMM launch
+# counters (tests/test_gpu_bf16_latency.py)
+PKLAUNCHES := catears_amd/lib/pk_am_launches
+$(PKLAUNCHES): tests/native/pk_am_launches.cc $(PKLIB) $(PKHDRS)
+	$(CXX) $(PKFLAGS) -o $@ $< -Lcatears_amd/lib -lcatears_pk -lcatears_hip -L/opt/rocm/lib -lamdhip64 \
+	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
+
 COMPATTEST := build/bin/compat_test
 $(COMPATTEST): tests/native/compat_test.cc $(wildcard $(HOST)/compat_src/*.cc) $(wildcard $(HOST)/compat/*.h)
 	@mkdir -p $(dir $@)
@@ -159,6 +166,6 @@ $(WIMGASAN): tests/native/weight_images_test.cc $(SRC)/weight_images.cc $(SRC)/w
 sanitize: $(COMPATASAN) $(FUZZASAN) $(RANGESASAN) $(WIMGASAN)
 .PHONY: sanitize
 
-host: $(PKLIB) $(PKTEST) $(COMPATTEST)
+host: $(PKLIB) $(PKTEST) $(PKLAUNCHES) $(COMPATTEST)
 all: host
 .PHONY: host

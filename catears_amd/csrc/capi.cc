@@ -277,6 +277,17 @@ int ce_gpu_i8_latency_plan(int kpad, int n, int rows, int *slices, int *k_steps_
   return CE_GPU_OK;
 }
 
+int ce_gpu_debug_bf16_latency_launches(int64_t *gemms) {
+  if (gemms) *gemms = b16_lat_launch_count();
+  return CE_GPU_OK;
+}
+
+int ce_gpu_bf16_latency_max_rows(int *max_rows) {
+  if (!max_rows) return fail(CE_GPU_EINVAL, "NULL argument");
+  *max_rows = b16_lat_max_rows();
+  return CE_GPU_OK;
+}
+
 int ce_gpu_trace_mark(int device, void *stream, int tag) {
   if (device < 0 || device >= 64 || tag < 1 || tag > 64) return fail(CE_GPU_EINVAL, "bad device or tag");
   CE_HIP(hipSetDevice(device));

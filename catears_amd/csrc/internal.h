@@ -330,6 +330,9 @@ struct X6Gemm {
   // ce_gpu_ctx_set_wide_tiles: the direct-weight kernel on 128 x 128 tiles
   // for every layer (twice the blocks of the 256 x 128 default)
   bool wide = false;
+  // plain bf16 (launch_gemm_bf16) on a latency context: up to kB16LatMaxRows
+  // rows the launch goes to kernels/gemm_bf16_lat.hip (the same bits)
+  bool lat = false;
 };
 
 // The last layer's slice partials when its reduce runs inside the finalize
@@ -568,6 +571,22 @@ int launch_gemm_bf16(hipStream_t s, const X6Gemm &a);
 // 128 x 128.  Same bits either way.
 constexpr int kB16LargeMinTiles = 64;
 bool bf16_small_tile(int rows, int n);
+// Latency mode of the mode (kernels/gemm_bf16_lat.hip): launch_gemm_bf16 with
+// a.lat set and a.m <= b16_lat_max_rows() runs gemm_bf16_lat_kernel, which
+// spreads a small row block over the chip by its outputs -- one wave per 16
+// units x 16 frames, operands straight from global memory into a register
+// ring, no LDS, no barrier -- with the same MFMA, K order, single accumulator
+// and epilogue: the bits of the kernels above, so the rule may depend on the
+// row count.  A function of a.m only.
+// kB16LatMaxRows: the largest row count of the sweep 70 / 140 / 280 / 640 /
+// 1024 / 2048 at which the kernel was measured faster than gemm_bf16_kernel
+// by more than the spread of the latter's two runs (TDNN-S per call,
+// DESIGN.md §8, profiles/r18_bf16_latency.json).
+constexpr int kB16LatMaxRows = 280;
+int b16_lat_max_rows();          // kB16LatMaxRows (experiments library: CATEARS_B16_LAT_MAXROWS)
+int64_t b16_lat_launch_count();  // gemm_bf16_lat_kernel launches of this process
+// launch_gemm_bf16's argument envelope
+int launch_gemm_bf16_lat(hipStream_t s, const X6Gemm &a);
 // splice_pad (below) written as bf16, out row r at out + r * po.
 int launch_splice_pad_bf16(hipStream_t s, const float *in, int ld_in, int rows, int din, int nseg, const int *off,
                            const int *row_map, uint16_t *out, int po);

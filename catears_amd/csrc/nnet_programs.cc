@@ -502,8 +502,11 @@ struct ChainX6 {
 };
 
 // Plain bf16 (kernels/gemm_bf16.hip, CE_GPU_GEMM_BF16): bf16 activations, the
-// fragment image's plane 0.  The context's latency and wide-tile settings are
-// not read: one kernel family, its tile a function of (rows, n).
+// fragment image's plane 0.  One kernel family, its tile a function of
+// (rows, n); on a latency context every Linear's launch carries X6Gemm::lat,
+// and launch_gemm_bf16 runs blocks of up to kB16LatMaxRows rows on
+// kernels/gemm_bf16_lat.hip (the same bits, no workspace of its own).  The
+// wide-tile setting is not read.
 struct ChainBf16 {
   using Args = X6Gemm;
   static constexpr int kWords = 1, kRound = 32;
@@ -512,9 +515,10 @@ struct ChainBf16 {
                     const int *row_map, uint16_t *out) {
     return launch_splice_pad_bf16(ctx->stream, x, ldx, rows, g.din, g.nseg, off, row_map, out, g.kpad);
   }
-  static void weights(ce_gpu_ctx *, const GemmLayer &g, Args &a) {
+  static void weights(ce_gpu_ctx *ctx, const GemmLayer &g, Args &a) {
     a.wd = g.wdir.as<uint16_t>();
     a.wd_kt = g.kpad / 32;
+    a.lat = ctx->latency != 0;
   }
   static int gemm(hipStream_t s, const Args &a) { return launch_gemm_bf16(s, a); }
 };

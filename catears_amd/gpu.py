@@ -43,6 +43,7 @@ ABI = [
     "ce_gpu_model_pad_widths", "ce_gpu_model_padded_widths",
     "ce_gpu_model_admit_row_ops", "ce_gpu_debug_rowop_chain",
     "ce_gpu_debug_rowop_chain_q", "ce_gpu_debug_i8_static_launches",
+    "ce_gpu_bf16_latency_max_rows", "ce_gpu_debug_bf16_latency_launches",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -142,6 +143,8 @@ def lib():
         "ce_gpu_debug_rowop_chain_q": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, ctypes.c_float, ctypes.c_int32, vp, ci,
                                             vp, vp]),
         "ce_gpu_debug_i8_static_launches": (ci, [pi64, pi64, pi64]),
+        "ce_gpu_bf16_latency_max_rows": (ci, [pi]),
+        "ce_gpu_debug_bf16_latency_launches": (ci, [pi64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -201,7 +204,9 @@ class Context:
         """Latency mode (ce_gpu_ctx_set_latency): split-K nnet GEMMs for small
         row blocks scored one at a time.  Static int8 models take their
         split-K pair up to the crossover of i8_latency_plan (the same bits as
-        off); dynamic int8 ignores the mode."""
+        off); plain bf16 models run row blocks of up to bf16_latency_max_rows()
+        rows on the latency kernel (no split-K: the same bits as off); dynamic
+        int8 ignores the mode."""
         check(lib().ce_gpu_ctx_set_latency(self.h, int(bool(on))))
 
     FBANK_MODES = {"exact": 0, "fast": 1}
@@ -546,6 +551,22 @@ def debug_i8_latency_launches():
     process so far."""
     n = ctypes.c_int64()
     check(lib().ce_gpu_debug_i8_latency_launches(ctypes.byref(n)))
+    return n.value
+
+
+def bf16_latency_max_rows():
+    """ce_gpu_bf16_latency_max_rows: the largest row block a plain bf16 Linear
+    runs on the latency kernel on a latency context.  Needs no device."""
+    n = ctypes.c_int()
+    check(lib().ce_gpu_bf16_latency_max_rows(ctypes.byref(n)))
+    return n.value
+
+
+def debug_bf16_latency_launches():
+    """ce_gpu_debug_bf16_latency_launches: plain bf16 latency GEMM launches of
+    this process so far."""
+    n = ctypes.c_int64()
+    check(lib().ce_gpu_debug_bf16_latency_launches(ctypes.byref(n)))
     return n.value
 
 

@@ -136,8 +136,23 @@ int ce_gpu_ctx_overflow(ce_gpu_ctx *ctx, int *overflow);
  * bits of the mode off for every split; larger blocks take the throughput
  * kernel automatically, and a caller may leave the mode on for any batch.
  *   Dynamic int8 models (ce_gpu_model_quantize) ignore the mode: their
- * parameters need a reduction over the block first. */
+ * parameters need a reduction over the block first.
+ *   Plain bf16 models (CE_GPU_GEMM_BF16): on, every Linear whose row block is
+ * at most ce_gpu_bf16_latency_max_rows rows (280) runs on a second kernel that
+ * spreads the block over the chip by its outputs -- one wave per 16 units x
+ * 16 frames, both operands loaded from global memory straight into a register
+ * ring, no LDS, no barrier -- instead of walking K behind one barrier per
+ * K-tile.  No split-K: the same MFMA per K-tile in ascending order into one
+ * accumulator and the same epilogue, so the rows are the bits of the mode
+ * off; larger blocks take the throughput kernels automatically, and a caller
+ * may leave the mode on for any batch. */
 int ce_gpu_ctx_set_latency(ce_gpu_ctx *ctx, int on);
+
+/* The largest row block that a plain bf16 Linear runs on the latency kernel
+ * when its context is in latency mode (the measured crossover), on the host
+ * (no device).  The rule depends on the row count only, which it may because
+ * the bits do not depend on the kernel.  CE_GPU_EINVAL for NULL. */
+int ce_gpu_bf16_latency_max_rows(int *max_rows);
 
 /* The slice rule of the static int8 latency mode, on the host (no device,
  * like ce_gpu_quant_params_from_range): a Linear of `kpad` K-bytes (its K
@@ -230,6 +245,8 @@ int ce_gpu_debug_counters(int64_t *device_allocs, int64_t *device_frees);
  * (i8_lat_gemm_kernel; counted on the host when one is enqueued): shows which
  * of the two int8 kernels a call took.  Measurement plumbing as above. */
 int ce_gpu_debug_i8_latency_launches(int64_t *gemms);
+/* The same for the plain bf16 latency GEMM (gemm_bf16_lat_kernel). */
+int ce_gpu_debug_bf16_latency_launches(int64_t *gemms);
 /* One launch of the kernel behind an admitted model's row steps
  * (ce_gpu_model_admit_row_ops), for tests and tools: the n_ops <= 4 row ops
  * h_ops (CE_GPU_ROW_*; h_scale[q] / h_offset[q] device vectors of a

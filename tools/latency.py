@@ -156,9 +156,87 @@ def static_int8(calls=200):
     print(json.dumps(res))
 
 
+def layer_us(ctx, model, x, out, calls=50):
+    """Median launch interval (us) of each GEMM of one nnet_propagate call
+    (ce_gpu_ctx_profile, class GEMM: the Linears behind the first one's
+    splice_pad launch and the first one itself, in program order)."""
+    ctx.profile(True, classes=[0])  # CE_GPU_PROF_GEMM
+    gpu.profile_anchor(0, torch.cuda.current_stream(0))
+    for _ in range(calls):
+        gpu.nnet_propagate(ctx, model, x, out=out)
+    iv = np.array(ctx.profile_intervals(0))
+    ctx.profile(False)
+    per = (iv[:, 1] - iv[:, 0]).reshape(calls, -1) * 1e3
+    return [round(float(v), 1) for v in np.median(per, axis=0)]
+
+
+def bf16(calls=300):
+    """TDNN-S in plain bf16 mode, one nnet_propagate per call: latency mode off
+    (gemm_bf16_kernel on 32 x 32 tiles) and on (gemm_bf16_lat_kernel up to
+    ce_gpu_bf16_latency_max_rows rows), beside the bf16x6 latency mode of the
+    fp32 model and the static int8 latency mode in the same run.  Per leg and
+    row count (LAT_ROWS, default 70) as static_int8(); the bf16 legs also give
+    their per-layer GEMM launch intervals, and off and on must agree in their
+    digests.  The legs alternate off / on / bf16x6 / int8 / on / off, so each
+    bf16 leg is measured twice.  LAT_LEGS restricts the legs."""
+    mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
+    conf = synth.write_model(mdir, "tdnn-s")
+    sizes = [int(v) for v in os.environ.get("LAT_ROWS", "70").split(",")]
+    legs = os.environ.get("LAT_LEGS", "off,on,bf16x6,int8,on,off").split(",")
+    ctxs = {k: gpu.Context(0) for k in ("off", "on", "bf16x6", "int8")}
+    for k in ("on", "bf16x6", "int8"):
+        ctxs[k].set_latency(True)
+    models = {"off": gpu.Model(ctxs["off"], conf).set_gemm("bf16"), "on": gpu.Model(ctxs["on"], conf).set_gemm("bf16"),
+              "bf16x6": gpu.Model(ctxs["bf16x6"], conf)}
+    if "int8" in legs:
+        cal = [synth.pcm(2900 + i, 48000) for i in range(4)]
+        m0 = gpu.Model(ctxs["int8"], conf)
+        plan = gpu.Plan(ctxs["int8"], [len(w) for w in cal], m0)
+        ranges = m0.calibrate(ctxs["int8"], plan,
+                              gpu.fbank(ctxs["int8"], plan, torch.from_numpy(np.concatenate(cal)).cuda()))
+        models["int8"] = m0.quantize_static(ctxs["int8"], ranges)
+    # absent from libraries older than the bf16 latency mode (A/B runs)
+    launches = getattr(gpu, "debug_bf16_latency_launches", lambda: 0)
+    max_rows = getattr(gpu, "bf16_latency_max_rows", lambda: 0)()
+    res = {"version": gpu.lib().ce_gpu_version().decode(), "device": torch.cuda.get_device_name(0), "calls": calls,
+           "bf16_latency_max_rows": max_rows}
+    names = {"off": "bf16_latency_off", "on": "bf16_latency_on", "bf16x6": "bf16x6_latency",
+             "int8": "static_int8_latency_on"}
+    for rows in sizes:
+        x = torch.from_numpy(np.random.default_rng(rows).normal(9, 3, size=(rows, 40)).astype(np.float32)).cuda()
+        for i, leg in enumerate(legs):
+            ctx, model = ctxs[leg], models[leg]
+            out = gpu.nnet_propagate(ctx, model, x)
+            for _ in range(20):
+                gpu.nnet_propagate(ctx, model, x, out=out)
+            n0 = launches()
+            us = per_call_us(lambda: gpu.nnet_propagate(ctx, model, x, out=out), calls)
+            n1 = launches()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                gpu.nnet_propagate(ctx, model, x, out=out)
+            b.record()
+            torch.cuda.synchronize()
+            digest = hashlib.sha1(out.cpu().numpy().tobytes()).hexdigest()[:12]
+            rec = {"p50_us": round(float(np.percentile(us, 50)), 1), "p10_us": round(float(np.percentile(us, 10)), 1),
+                   "p90_us": round(float(np.percentile(us, 90)), 1),
+                   "back_to_back_us": round(a.elapsed_time(b) * 1e3 / calls, 1), "sha1": digest,
+                   "bf16_latency_gemms_per_call": (n1 - n0) / calls}
+            if leg in ("off", "on"):
+                rec["gemm_layer_us"] = layer_us(ctx, model, x, out)
+            res[f"{names[leg]}/{rows}/run{i}"] = rec
+            print(f"{names[leg]:24s} rows {rows:5d}: p50 {rec['p50_us']:7.1f} us  [{rec['p10_us']:.1f}, {rec['p90_us']:.1f}]"
+                  f"  back to back {rec['back_to_back_us']:7.1f} us  latency GEMMs/call "
+                  f"{rec['bf16_latency_gemms_per_call']:.0f}  out {digest}  {rec.get('gemm_layer_us', '')}", flush=True)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
     nums = [int(v) for v in sys.argv[1:] if not v.startswith("--")]
-    if "--static-int8" in sys.argv[1:]:
+    if "--bf16" in sys.argv[1:]:
+        bf16(*nums[:1])
+    elif "--static-int8" in sys.argv[1:]:
         static_int8(*nums[:1])
     else:
         main(*nums[:1])

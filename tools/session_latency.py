@@ -24,7 +24,11 @@ Both legs compute the same rows (checked once per N, bit for bit).
       on a latency-mode context, see static_int8()
   python tools/session_latency.py --incremental [--slots N] [--tick-ms T] [ticks] [rounds]
       an incremental set (CE_GPU_SESSIONS_INCREMENTAL) beside a plain one,
-      in three forms of the model, see incremental()"""
+      in three forms of the model, see incremental()
+  python tools/session_latency.py --incremental --bf16 [--slots N] [--tick-ms T] [ticks] [rounds]
+      the same for the plain bf16 model alone, on a throughput context (form
+      bf16) and on a latency context (form bf16_latency: pushes that pack at
+      most ce_gpu_bf16_latency_max_rows rows run on the latency kernel)"""
 import json
 import os
 import sys
@@ -242,7 +246,7 @@ def incremental(ticks=100, rounds=3, n=64, tick_ms=100, forms=("static_int8_late
             model = gpu.Model(ctx, image=image, prior=prior) if renorm else gpu.Model(ctx, conf)
             if form not in ("bf16", "static_int8"):
                 ctx.set_latency(True)
-            if form == "bf16":
+            if form in ("bf16", "bf16_latency"):
                 model.set_gemm("bf16")
             if form in ("static_int8_latency", "static_int8"):
                 plan = gpu.Plan(ctx, [len(w) for w in cal], model)
@@ -255,6 +259,9 @@ def incremental(ticks=100, rounds=3, n=64, tick_ms=100, forms=("static_int8_late
         out = torch.empty((n * (chunk // 160 + 1), legs[0][1].num_pdfs), dtype=torch.float32, device="cuda")
         times, packed, last = ([], []), [0, 0], [None, None]
         counters = None
+        # absent from libraries older than the bf16 latency mode (A/B runs)
+        b16_launches = getattr(gpu, "debug_bf16_latency_launches", lambda: 0)
+        b16_0 = b16_launches()
         for r in range(rounds + 1):
             for k, (ctx, _, sess) in enumerate(legs):
                 before = sess.stats()
@@ -273,6 +280,7 @@ def incremental(ticks=100, rounds=3, n=64, tick_ms=100, forms=("static_int8_late
         rec = {"form": form, "slots": n, "tick_ms": tick_ms, "timed_pushes": len(times[0]),
                "lead_rows": legs[0][2].stats()["lead_rows"],
                "pushes_allocated_nothing": gpu.debug_counters() == counters,
+               "bf16_latency_gemm_launches": b16_launches() - b16_0,
                "rows_identical": bool(np.array_equal(last[0][0].view(np.uint32), last[1][0].view(np.uint32)))}
         for k, name in enumerate(("incremental", "plain")):
             v = times[k]
@@ -297,6 +305,9 @@ if __name__ == "__main__":
     if "--static-int8" in argv and "--renorm" in argv:
         incremental(*(nums + [100, 3][len(nums):]), n=flag("--slots", 64), tick_ms=flag("--tick-ms", 100),
                     forms=("static_int8_latency", "static_int8"), renorm=True)
+    elif "--incremental" in argv and "--bf16" in argv:
+        incremental(*(nums + [100, 3][len(nums):]), n=flag("--slots", 64), tick_ms=flag("--tick-ms", 100),
+                    forms=("bf16", "bf16_latency"))
     elif "--incremental" in argv:
         incremental(*(nums + [100, 3][len(nums):]), n=flag("--slots", 64), tick_ms=flag("--tick-ms", 100))
     elif "--static-int8" in sys.argv[1:]:
