@@ -35,6 +35,19 @@ static std::atomic<int64_t> g_device_allocs{0}, g_device_frees{0};
 void count_device_alloc() { g_device_allocs.fetch_add(1, std::memory_order_relaxed); }
 void count_device_free() { g_device_frees.fetch_add(1, std::memory_order_relaxed); }
 
+// ce_gpu_debug_fill_allocs
+static std::atomic<int> g_fill_allocs{0};
+static std::atomic<uint32_t> g_fill_word{0};
+
+int debug_fill(hipStream_t s, void *p, size_t bytes, uint32_t word, int64_t *total) {
+  if (!p || bytes == 0) return CE_GPU_OK;
+  const size_t words = bytes / 4, rest = bytes % 4;
+  if (words) CE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)word, words, s));
+  if (rest) CE_HIP(hipMemsetAsync(static_cast<char *>(p) + words * 4, (int)(word & 0xff), rest, s));
+  if (total) *total += (int64_t)bytes;
+  return CE_GPU_OK;
+}
+
 int DevBuf::alloc(size_t n) {
   release();
   if (n == 0) return CE_GPU_OK;
@@ -46,6 +59,13 @@ int DevBuf::alloc(size_t n) {
   }
   count_device_alloc();
   bytes = n;
+  if (g_fill_allocs.load(std::memory_order_relaxed)) {
+    // ce_gpu_debug_fill_allocs: nothing may take a fresh allocation for zeros.
+    // The null stream and a device-wide wait: the buffer's first user may be
+    // on any stream, a non-blocking one included.
+    CE_TRY(debug_fill(nullptr, ptr, n, g_fill_word.load(std::memory_order_relaxed)));
+    CE_HIP(hipDeviceSynchronize());
+  }
   return CE_GPU_OK;
 }
 
@@ -798,6 +818,24 @@ int ce_gpu_debug_rowop_chain_q(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int
 
 int ce_gpu_debug_i8_static_launches(int64_t *quantize_passes, int64_t *row_launches, int64_t *row_launches_q) {
   i8_static_launch_counts(quantize_passes, row_launches, row_launches_q);
+  return CE_GPU_OK;
+}
+
+int ce_gpu_debug_fill_allocs(int on, uint32_t word) {
+  g_fill_word.store(word, std::memory_order_relaxed);
+  g_fill_allocs.store(on ? 1 : 0, std::memory_order_relaxed);
+  return CE_GPU_OK;
+}
+
+int ce_gpu_debug_fill_ctx(ce_gpu_ctx *ctx, uint32_t word, int64_t *bytes) {
+  if (!ctx) return fail(CE_GPU_EINVAL, "ctx is NULL");
+  CE_HIP(hipSetDevice(ctx->device));
+  int64_t total = 0;
+  // every buffer a call writes before it reads (the header names them and
+  // the three it leaves alone: d_tables, overflow, lat_tickets)
+  for (const DevBuf *b : {&ctx->workspace, &ctx->scratch, &ctx->lat_part, &ctx->blk_maps, &ctx->debug_qp})
+    CE_TRY(debug_fill(ctx->stream, b->ptr, b->bytes, word, &total));
+  if (bytes) *bytes = total;
   return CE_GPU_OK;
 }
 

@@ -79,6 +79,11 @@ struct DevBuf {
 void count_device_alloc();
 void count_device_free();
 
+// ce_gpu_debug_fill_*: `bytes` bytes at p (4-byte aligned) set to `word` on
+// stream s, a trailing 1-3 bytes to its low byte; *total (optional) grows by
+// what was filled.  Enqueues only.
+int debug_fill(hipStream_t s, void *p, size_t bytes, uint32_t word, int64_t *total = nullptr);
+
 // ------------------------------------------------------------ fbank tables --
 
 // Fixed fbank geometry (src/fbank.h:7-13).

@@ -553,6 +553,32 @@ int ce_gpu_sessions_reset(ce_gpu_sessions *s, int slot) {
   return CE_GPU_OK;
 }
 
+int ce_gpu_debug_fill_sessions(ce_gpu_sessions *s, uint32_t word, int n, const int32_t *h_slots) {
+  if (!s || n < 0 || (n > 0 && !h_slots)) return fail(CE_GPU_EINVAL, "debug_fill_sessions: bad argument");
+  for (int i = 0; i < n; ++i)
+    if (h_slots[i] < 0 || h_slots[i] >= s->n_slots) return fail(CE_GPU_EINVAL, fmt("debug_fill_sessions: no slot %d", h_slots[i]));
+  CE_HIP(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  // per-push scratch: a push writes what it reads of both
+  CE_TRY(debug_fill(st, s->tmp.ptr, s->tmp.bytes, word));
+  CE_TRY(debug_fill(st, s->desc.ptr, s->desc.bytes, word));
+  const size_t f = sizeof(float);
+  for (int i = 0; i < n; ++i) {
+    const size_t k = (size_t)h_slots[i];
+    CE_TRY(debug_fill(st, s->stage.as<float>() + k * s->stride, (size_t)s->stride * f, word));
+    CE_TRY(debug_fill(st, s->norm.as<float>() + k * s->norm_cap * kMel, (size_t)s->norm_cap * kMel * f, word));
+    if (s->raw.ptr) CE_TRY(debug_fill(st, s->raw.as<float>() + k * s->raw_cap * kMel, (size_t)s->raw_cap * kMel * f, word));
+    if (s->carry.ptr) CE_TRY(debug_fill(st, s->carry.as<float>() + k * kMel, kMel * f, word));
+    // incremental: the slot's c rows of every cached layer (IncrLayer)
+    for (const IncrLayer &l : s->layers) {
+      if (!l.cache) continue;
+      CE_TRY(debug_fill(st, l.cache + k * l.c * l.row_cap, (size_t)l.c * l.row_cap, word));
+      CE_TRY(debug_fill(st, l.sums + k * l.c, (size_t)l.c * sizeof(int32_t), word));
+    }
+  }
+  return CE_GPU_OK;
+}
+
 int ce_gpu_sessions_push(ce_gpu_sessions *s, int n, const int32_t *h_slot, const int32_t *h_num_samples,
                          const int32_t *h_flags, const float *d_pcm, float *d_loglik, int64_t capacity_rows,
                          int32_t *h_rows_out) {

@@ -44,6 +44,7 @@ ABI = [
     "ce_gpu_model_admit_row_ops", "ce_gpu_debug_rowop_chain",
     "ce_gpu_debug_rowop_chain_q", "ce_gpu_debug_i8_static_launches",
     "ce_gpu_bf16_latency_max_rows", "ce_gpu_debug_bf16_latency_launches",
+    "ce_gpu_debug_fill_allocs", "ce_gpu_debug_fill_ctx", "ce_gpu_debug_fill_sessions",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -145,6 +146,9 @@ def lib():
         "ce_gpu_debug_i8_static_launches": (ci, [pi64, pi64, pi64]),
         "ce_gpu_bf16_latency_max_rows": (ci, [pi]),
         "ce_gpu_debug_bf16_latency_launches": (ci, [pi64]),
+        "ce_gpu_debug_fill_allocs": (ci, [ci, ctypes.c_uint32]),
+        "ce_gpu_debug_fill_ctx": (ci, [vp, ctypes.c_uint32, pi64]),
+        "ce_gpu_debug_fill_sessions": (ci, [vp, ctypes.c_uint32, ci, pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -577,6 +581,31 @@ def debug_i8_static_launches():
     q, r, rq = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
     check(lib().ce_gpu_debug_i8_static_launches(ctypes.byref(q), ctypes.byref(r), ctypes.byref(rq)))
     return q.value, r.value, rq.value
+
+
+def debug_fill_allocs(on, word=0):
+    """ce_gpu_debug_fill_allocs: while on, every device allocation the
+    library makes in this process is filled with the 32-bit `word` before it
+    is used (debug only; off by default)."""
+    check(lib().ce_gpu_debug_fill_allocs(int(bool(on)), int(word) & 0xffffffff))
+
+
+def debug_fill_ctx(ctx, word):
+    """ce_gpu_debug_fill_ctx: fills the context's call-scoped device buffers
+    (workspace, scratch, latency partials, block maps) with `word` on its
+    stream; returns the bytes filled.  Debug only."""
+    n = ctypes.c_int64()
+    check(lib().ce_gpu_debug_fill_ctx(ctx.h, int(word) & 0xffffffff, ctypes.byref(n)))
+    return n.value
+
+
+def debug_fill_sessions(sessions, word, slots=()):
+    """ce_gpu_debug_fill_sessions: fills the set's per-push scratch and every
+    device region of the listed slots with `word` (a live slot's later rows
+    are then garbage).  Debug only."""
+    sl = np.ascontiguousarray(list(slots), np.int32)
+    check(lib().ce_gpu_debug_fill_sessions(sessions.h, int(word) & 0xffffffff, len(sl),
+                                           sl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
 
 
 class Sessions:

@@ -280,6 +280,41 @@ int ce_gpu_debug_rowop_chain_q(ce_gpu_ctx *ctx, int n_ops, const int *h_ops, int
  * of a quantize pass.  Shows which hand-over a model's layers took.  Any
  * pointer may be NULL.  Measurement plumbing as above. */
 int ce_gpu_debug_i8_static_launches(int64_t *quantize_passes, int64_t *row_launches, int64_t *row_launches_q);
+/* Hostile residue for tests (tests/test_gpu_stale_memory.py): the three
+ * entries below overwrite device memory the library owns with a 32-bit word
+ * of the caller's choice, so that a call which reads such memory before it
+ * has written it gives different bits.  Debug only: no product path calls
+ * them, and nothing here reads the environment.
+ *
+ * ce_gpu_debug_fill_allocs is process-wide, like the counters above.  While
+ * `on` is nonzero every device allocation the library makes (contexts,
+ * models, plans, session sets, workspaces as they grow) is filled with `word`
+ * before the allocating call goes on -- the fill is complete when the
+ * allocation returns (a trailing 1-3 bytes take the word's low byte).  Off by
+ * default; off costs one relaxed atomic load per allocation. */
+int ce_gpu_debug_fill_allocs(int on, uint32_t word);
+/* Fills, on the context's stream, every device buffer of the context that a
+ * call must write before it reads: the nnet activation workspace, the scratch
+ * buffer (the spliced first-layer block, int8 operand bytes, row sums,
+ * parameters and min / max partials, ce_gpu_quantize's and the u8 GEMM's
+ * partials), the latency GEMMs' slice partials, the row maps of
+ * ce_gpu_nnet_propagate_blocks and the parameter record of
+ * ce_gpu_debug_rowop_chain_q -- whichever of them exist.  Left alone, because
+ * they carry an invariant from one call to the next: the fbank tables
+ * (constant since ce_gpu_ctx_create), the f16x3 overflow word (sticky until
+ * ce_gpu_ctx_overflow reads it) and the experiments library's split-K tickets
+ * (zero between launches by construction).  *bytes (may be NULL) receives the
+ * bytes filled. */
+int ce_gpu_debug_fill_ctx(ce_gpu_ctx *ctx, uint32_t word, int64_t *bytes);
+/* Fills, on the stream of the set's context, the set's per-push scratch (the
+ * fbank temporary and the device copy of the push descriptor) and, for each
+ * of the n slots h_slots names, that slot's regions of the staging buffer,
+ * the raw and normalised feature rings and the CMVN carry, and in an
+ * incremental set its cached context rows and their row sums.  Meant for a
+ * slot after ce_gpu_sessions_reset, which must read none of them before it
+ * has rewritten them.  Any slot may be listed: a live slot's later rows are
+ * then garbage by design.  n == 0 fills the per-push scratch alone. */
+int ce_gpu_debug_fill_sessions(ce_gpu_sessions *s, uint32_t word, int n, const int32_t *h_slots);
 
 /* -------------------------------------------------------------- model --- */
 
