@@ -37,7 +37,7 @@ HOSTFLAGS := -O2 -fPIC -std=c++17 -ffp-contract=off -Iinclude -I$(SRC) -I/opt/ro
 
 KERNELS := $(wildcard $(SRC)/kernels/*.hip)
 HOSTSRC := $(SRC)/capi.cc $(SRC)/tables.cc $(SRC)/model_io.cc $(SRC)/sessions.cc \
-           $(SRC)/nnet_programs.cc $(SRC)/model.cc $(SRC)/weight_images.cc
+           $(SRC)/nnet_programs.cc $(SRC)/model.cc $(SRC)/weight_images.cc $(SRC)/plans.cc
 OBJS := $(patsubst $(SRC)/kernels/%.hip,$(OBJ)/%.o,$(KERNELS)) \
         $(patsubst $(SRC)/%.cc,$(OBJ)/cc/%.o,$(HOSTSRC))
 HDRS := include/catears_gpu.h $(SRC)/internal.h $(SRC)/model_io.h $(SRC)/fbank_ops.h $(SRC)/fbank8_ops.h $(SRC)/tile_order.h $(SRC)/lds_dma.h $(SRC)/bf16_split.h $(SRC)/gemm_bf16x6_kernels.h $(SRC)/gemm_bf16_kernels.h $(SRC)/cmvn_ops.h $(SRC)/i8_ops.h $(SRC)/nnet_i8_kernels.h $(SRC)/nnet_programs.h $(SRC)/weight_images.h
@@ -125,6 +125,13 @@ $(PKLAUNCHES): tests/native/pk_am_launches.cc $(PKLIB) $(PKHDRS)
 	$(CXX) $(PKFLAGS) -o $@ $< -Lcatears_amd/lib -lcatears_pk -lcatears_hip -L/opt/rocm/lib -lamdhip64 \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
+# Fbank::Process over a stream of pieces and CMVN twice, with the library's
+# allocation counters around them (tests/test_gpu_dropin_plans.py)
+PKSTREAM := catears_amd/lib/pk_fbank_stream
+$(PKSTREAM): tests/native/pk_fbank_stream.cc $(PKLIB) $(PKHDRS)
+	$(CXX) $(PKFLAGS) -pthread -o $@ $< -Lcatears_amd/lib -lcatears_pk -lcatears_hip -L/opt/rocm/lib -lamdhip64 \
+	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
+
 COMPATTEST := build/bin/compat_test
 $(COMPATTEST): tests/native/compat_test.cc $(wildcard $(HOST)/compat_src/*.cc) $(wildcard $(HOST)/compat/*.h)
 	@mkdir -p $(dir $@)
@@ -166,6 +173,6 @@ $(WIMGASAN): tests/native/weight_images_test.cc $(SRC)/weight_images.cc $(SRC)/w
 sanitize: $(COMPATASAN) $(FUZZASAN) $(RANGESASAN) $(WIMGASAN)
 .PHONY: sanitize
 
-host: $(PKLIB) $(PKTEST) $(PKLAUNCHES) $(COMPATTEST)
+host: $(PKLIB) $(PKTEST) $(PKLAUNCHES) $(PKSTREAM) $(COMPATTEST)
 all: host
 .PHONY: host

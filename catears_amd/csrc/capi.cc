@@ -358,6 +358,8 @@ int ce_gpu_plan_create(ce_gpu_ctx *ctx, const ce_gpu_model *model, const int64_t
   CE_HIP(hipSetDevice(ctx->device));
   std::unique_ptr<ce_gpu_plan> p(new (std::nothrow) ce_gpu_plan());
   if (!p) return fail(CE_GPU_ENOMEM, "out of host memory");
+  p->ctx = ctx;
+  p->device = ctx->device;
   p->n_utt = n_utt;
   p->sample_off.assign(n_utt + 1, 0);
   p->frame_off.assign(n_utt + 1, 0);
@@ -455,6 +457,7 @@ int ce_gpu_plan_frame_offsets(const ce_gpu_plan *p, int64_t *h_out) {
 }
 
 int ce_gpu_plan_destroy(ce_gpu_plan *p) {
+  if (p) plan_release_ring(p);  // a reusable plan's pinned descriptor ring (plans.cc)
   delete p;
   return CE_GPU_OK;
 }

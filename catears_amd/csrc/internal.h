@@ -462,6 +462,27 @@ struct ce_gpu_plan {
   int max_chunk_rows = 0;
   int left = 0, right = 0;
   bool has_model = false;
+  // ce_gpu_plan_create_reusable (plans.cc): the tables above are sized for a
+  // capacity and rewritten by plan_expand_kernel per ce_gpu_plan_assign; the
+  // launches read only what the current assignment wrote (n_utt, total_frames
+  // and the chunk list bound every index).
+  struct RingEntry {
+    void *host = nullptr;         // pinned descriptor image
+    hipEvent_t copied = nullptr;  // its copy to d_desc has run
+    bool in_use = false;
+  };
+  bool reusable = false;
+  ce_gpu_ctx *ctx = nullptr;   // the context whose stream orders the assignments
+  int device = 0;
+  int max_utts = 0, max_rows = 0;
+  int64_t max_total_samples = 0;
+  int64_t max_segs = 0, max_packed = 0;  // most segments / packed rows of any assignment
+  int64_t packed = 0;                    // packed rows of the current one
+  catears::DevBuf d_desc;                // device copy of the descriptor (stream-ordered)
+  size_t desc_bytes = 0;
+  std::vector<RingEntry> ring;
+  int ring_at = 0;
+  std::vector<Chunk> next_chunks;        // the chunk list of an assignment until it is enqueued
 };
 
 namespace catears {
@@ -752,6 +773,36 @@ int score_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, const float *feats
 // `rows` packed rows in any GEMM mode and in latency mode, so that later
 // calls of up to that many rows allocate nothing.
 int reserve_packed_rows(ce_gpu_ctx *ctx, const ce_gpu_model *m, int rows);
+
+// ---- reusable plans (plans.cc, kernels/plan_expand.hip) ----
+
+// One packed segment of an assignment (device image, written by the host):
+// frames t .. t + n - 1 of utterance utt with their L + R context rows, at
+// packed rows base .. base + n + L + R - 1 of the row tables.
+struct PlanSeg {
+  int32_t utt;
+  int32_t t;
+  int32_t n;
+  int32_t base;
+};
+// The descriptor of one assignment, as ce_gpu_plan_assign lays it out in a
+// pinned ring entry and copies it to the plan's d_desc: sample_off and
+// frame_off (n_utt + 1 int64 each), then the segments.
+inline size_t plan_desc_seg_offset(int n_utt) { return 16 * (size_t)(n_utt + 1); }
+inline size_t plan_desc_bytes(int n_utt, int64_t n_seg) {
+  return plan_desc_seg_offset(n_utt) + sizeof(PlanSeg) * (size_t)n_seg;
+}
+// Expands the descriptor at d_desc into the plan's six tables: the words
+// ce_gpu_plan_create's host loops give for the same lengths.  fb_blocks:
+// fbank blocks of the assignment (block_utt[0] = 0 is written for none);
+// packed: packed rows (0 without a model).
+int launch_plan_expand(hipStream_t s, const void *d_desc, int n_utt, int64_t n_seg, int64_t fb_blocks,
+                       int64_t packed, int left, int right, int64_t *d_sample_off, int64_t *d_frame_off,
+                       int32_t *d_block_utt, int32_t *d_row_src, int32_t *d_row_dst, uint32_t *d_row_edge);
+// Depth of a reusable plan's pinned descriptor ring.
+constexpr int kPlanRing = 8;
+// Releases a reusable plan's ring (waits for the copies still in flight).
+void plan_release_ring(ce_gpu_plan *p);
 
 // One pushed slot of a session push (device image, written by the host).
 struct SessionPush {

@@ -45,6 +45,7 @@ ABI = [
     "ce_gpu_debug_rowop_chain_q", "ce_gpu_debug_i8_static_launches",
     "ce_gpu_bf16_latency_max_rows", "ce_gpu_debug_bf16_latency_launches",
     "ce_gpu_debug_fill_allocs", "ce_gpu_debug_fill_ctx", "ce_gpu_debug_fill_sessions",
+    "ce_gpu_plan_create_reusable", "ce_gpu_plan_assign", "ce_gpu_plan_capacity", "ce_gpu_debug_plan_tables",
 ]
 
 # ce_gpu_model_set_gemm modes
@@ -149,6 +150,10 @@ def lib():
         "ce_gpu_debug_fill_allocs": (ci, [ci, ctypes.c_uint32]),
         "ce_gpu_debug_fill_ctx": (ci, [vp, ctypes.c_uint32, pi64]),
         "ce_gpu_debug_fill_sessions": (ci, [vp, ctypes.c_uint32, ci, pi32]),
+        "ce_gpu_plan_create_reusable": (ci, [vp, vp, ci, i64, ci, pp]),
+        "ce_gpu_plan_assign": (ci, [vp, pi64, ci]),
+        "ce_gpu_plan_capacity": (ci, [ci, i64, ci, ci, ci, pi64, pi64, pi64]),
+        "ce_gpu_debug_plan_tables": (ci, [vp, ci, vp, i64, pi64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -457,6 +462,49 @@ def num_frames(n_samples):
     return lib().ce_gpu_fbank_num_frames(int(n_samples))
 
 
+def _plan_capacity_args(max_utts, max_total_samples, max_rows):
+    """The capacity of Plan.reusable as ints; ValueError for what
+    ce_gpu_plan_create_reusable would refuse whatever the model."""
+    max_utts, max_total_samples, max_rows = int(max_utts), int(max_total_samples), int(max_rows)
+    if max_utts <= 0 or max_utts >= 2 ** 31:
+        raise ValueError(f"max_utts must be in 1 .. 2^31 - 1, got {max_utts}")
+    if max_total_samples <= 0 or max_total_samples >= 2 ** 63:
+        raise ValueError(f"max_total_samples must be positive (and fit int64), got {max_total_samples}")
+    if max_rows >= 2 ** 31:
+        raise ValueError(f"max_rows must fit an int, got {max_rows}")
+    return max_utts, max_total_samples, max_rows
+
+
+def _plan_lengths(num_samples, max_utts, max_total_samples):
+    """The lengths of Plan.assign as a contiguous int64 vector; ValueError
+    for what ce_gpu_plan_assign would refuse (a negative length, more than
+    max_utts utterances or max_total_samples samples) and for lengths that
+    are no whole numbers."""
+    a = np.asarray(num_samples)
+    if a.ndim != 1:
+        raise ValueError("num_samples must be a 1-D sequence of sample counts")
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"num_samples must be integers, got dtype {a.dtype}")
+    ns = np.ascontiguousarray(a, np.int64)
+    if len(ns) > max_utts:
+        raise ValueError(f"{len(ns)} utterances, the plan's max_utts is {max_utts}")
+    if len(ns) and int(ns.min()) < 0:
+        raise ValueError("negative sample count")
+    if sum(int(n) for n in ns) > max_total_samples:
+        raise ValueError(f"more than the plan's max_total_samples ({max_total_samples}) samples")
+    return ns
+
+
+def plan_capacity(max_utts, max_total_samples, left, right, max_rows=4096):
+    """ce_gpu_plan_capacity: (frames, segments, packed rows) a reusable plan
+    of this capacity reserves for a model of context (left, right).  Needs no
+    device."""
+    f, s, r = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    check(lib().ce_gpu_plan_capacity(int(max_utts), int(max_total_samples), int(max_rows), int(left), int(right),
+                                     ctypes.byref(f), ctypes.byref(s), ctypes.byref(r)))
+    return f.value, s.value, r.value
+
+
 class Plan:
     def __init__(self, ctx, num_samples, model=None, max_rows=4096):
         ns = np.ascontiguousarray(num_samples, np.int64)
@@ -465,6 +513,11 @@ class Plan:
                                        ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                        len(ns), max_rows, ctypes.byref(h)))
         self.h = h
+        self.is_reusable = False
+        self._refresh()
+
+    def _refresh(self):
+        h = self.h
         a, d, e = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         b, c = ctypes.c_int64(), ctypes.c_int64()
         check(lib().ce_gpu_plan_info(h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
@@ -474,6 +527,35 @@ class Plan:
         off = np.zeros(self.n_utt + 1, np.int64)
         check(lib().ce_gpu_plan_frame_offsets(h, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         self.frame_offsets = off
+
+    @classmethod
+    def reusable(cls, ctx, max_utts, max_total_samples, model=None, max_rows=4096):
+        """ce_gpu_plan_create_reusable: a plan for any lengths of at most
+        `max_utts` utterances and `max_total_samples` samples in all, empty
+        until assign().  Keeps a reference to `ctx`, which it is bound to."""
+        max_utts, max_total_samples, max_rows = _plan_capacity_args(max_utts, max_total_samples, max_rows)
+        self = cls.__new__(cls)
+        self.h = None
+        h = ctypes.c_void_p()
+        check(lib().ce_gpu_plan_create_reusable(ctx.h, model.h if model else None, max_utts, max_total_samples,
+                                                max_rows, ctypes.byref(h)))
+        self.h = h
+        self.is_reusable = True
+        self.max_utts, self.max_total_samples = max_utts, max_total_samples
+        self._ctx = ctx
+        self._refresh()
+        return self
+
+    def assign(self, num_samples):
+        """ce_gpu_plan_assign: replaces the lengths (stream-ordered, no
+        allocation) and refreshes n_utt, total_samples, total_frames,
+        n_chunks, max_chunk_rows and frame_offsets."""
+        if not getattr(self, "is_reusable", False):
+            raise ValueError("assign needs a plan from Plan.reusable (this one is immutable)")
+        ns = _plan_lengths(num_samples, self.max_utts, self.max_total_samples)
+        check(lib().ce_gpu_plan_assign(self.h, ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(ns)))
+        self._refresh()
+        return self
 
     def close(self):
         if getattr(self, "h", None):
@@ -606,6 +688,26 @@ def debug_fill_sessions(sessions, word, slots=()):
     sl = np.ascontiguousarray(list(slots), np.int32)
     check(lib().ce_gpu_debug_fill_sessions(sessions.h, int(word) & 0xffffffff, len(sl),
                                            sl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+
+
+PLAN_TABLES = (("sample_off", np.int64), ("frame_off", np.int64), ("block_utt", np.int32),
+               ("row_src", np.int32), ("row_dst", np.int32), ("row_edge", np.uint32))
+
+
+def debug_plan_tables(plan):
+    """ce_gpu_debug_plan_tables: the plan's six device tables as numpy
+    arrays by name (PLAN_TABLES), each as long as the current assignment
+    uses.  Synchronizes the plan's context.  Debug only."""
+    out = {}
+    for which, (name, dtype) in enumerate(PLAN_TABLES):
+        n = ctypes.c_int64()
+        check(lib().ce_gpu_debug_plan_tables(plan.h, which, None, 0, ctypes.byref(n)))  # the length alone
+        a = np.empty(n.value // np.dtype(dtype).itemsize, dtype)
+        if n.value:
+            check(lib().ce_gpu_debug_plan_tables(plan.h, which, a.ctypes.data_as(ctypes.c_void_p), a.nbytes,
+                                                 ctypes.byref(n)))
+        out[name] = a
+    return out
 
 
 class Sessions:

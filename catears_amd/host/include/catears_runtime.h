@@ -86,6 +86,11 @@ class Runtime {
     Lease(Lane *lane, std::unique_lock<std::mutex> lock) : lane_(lane), lock_(std::move(lock)) {}
     ce_gpu_ctx *ctx() const;
     DeviceBuffer &scratch(int slot);
+    // The lane's own reusable plan (ce_gpu_plan_create_reusable, no model)
+    // assigned to one utterance of `samples` samples: no allocation, release
+    // or synchronization unless the call exceeds the plan's capacity, which
+    // then grows geometrically.  Valid until the lane's next Plan call.
+    const ce_gpu_plan *Plan(int64_t samples);
     // as Runtime::Upload / Download, on the lane's stream
     void Upload(void *dst, size_t dst_ld, const void *src, size_t src_ld, size_t elem, size_t rows, size_t cols);
     void Download(void *dst, size_t dst_ld, const void *src, size_t src_ld, size_t elem, size_t rows, size_t cols);

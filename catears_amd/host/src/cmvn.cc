@@ -24,16 +24,14 @@ CMVN::CMVN(const Vector<float> &global_stats, const Matrix<float> &raw_feats) {
   // a one-utterance plan whose frame count is num_frames_
   const int64_t samples = CE_GPU_FRAME_LENGTH + (int64_t)CE_GPU_FRAME_SHIFT * (num_frames_ - 1);
   Runtime::Lease lane = Runtime::Get().Acquire();
-  ce_gpu_plan *raw = nullptr;
-  Check(ce_gpu_plan_create(lane.ctx(), nullptr, &samples, 1, 0, &raw), "CMVN");
-  std::unique_ptr<ce_gpu_plan, int (*)(ce_gpu_plan *)> plan(raw, ce_gpu_plan_destroy);
+  const ce_gpu_plan *plan = lane.Plan(samples);  // the lane's reusable plan: nothing allocated once warm
   const size_t n = (size_t)num_frames_ * PK_FBANK_DIM;
   float *d_in = static_cast<float *>(lane.scratch(0).Reserve(sizeof(float) * n));
   float *d_out = static_cast<float *>(lane.scratch(1).Reserve(sizeof(float) * n));
   float *d_stats = static_cast<float *>(lane.scratch(2).Reserve(sizeof(float) * (PK_FBANK_DIM + 1)));
   lane.Upload(d_in, PK_FBANK_DIM, raw_feats.Data(), raw_feats.Stride(), sizeof(float), num_frames_, PK_FBANK_DIM);
   lane.Upload(d_stats, PK_FBANK_DIM + 1, global_stats.Data(), PK_FBANK_DIM + 1, sizeof(float), 1, PK_FBANK_DIM + 1);
-  Check(ce_gpu_cmvn(lane.ctx(), plan.get(), d_stats, d_in, d_out), "CMVN");
+  Check(ce_gpu_cmvn(lane.ctx(), plan, d_stats, d_in, d_out), "CMVN");
   lane.Download(normalized_.data(), PK_FBANK_DIM, d_out, PK_FBANK_DIM, sizeof(float), num_frames_, PK_FBANK_DIM);
 }
 

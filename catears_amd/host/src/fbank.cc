@@ -27,13 +27,13 @@ void Fbank::Process(Instance *inst, const VectorBase<float> &wave, Matrix<float>
   fbank_feature->Resize((int)frames, PK_FBANK_DIM, Matrix<float>::kUndefined);
   {
     Runtime::Lease lane = Runtime::Get().Acquire();
-    ce_gpu_plan *raw = nullptr;
-    Check(ce_gpu_plan_create(lane.ctx(), nullptr, &samples, 1, 0, &raw), "Fbank::Process");
-    std::unique_ptr<ce_gpu_plan, int (*)(ce_gpu_plan *)> plan(raw, ce_gpu_plan_destroy);
+    // the lane's reusable plan rebound to this call's length: once warm no
+    // allocation, release or null-stream copy (a plan per call made six)
+    const ce_gpu_plan *plan = lane.Plan(samples);
     float *d_pcm = static_cast<float *>(lane.scratch(0).Reserve(sizeof(float) * samples));
     float *d_feat = static_cast<float *>(lane.scratch(1).Reserve(sizeof(float) * frames * PK_FBANK_DIM));
     lane.Upload(d_pcm, samples, buf.data(), samples, sizeof(float), 1, samples);
-    Check(ce_gpu_fbank(lane.ctx(), plan.get(), d_pcm, d_feat, nullptr), "Fbank::Process");
+    Check(ce_gpu_fbank(lane.ctx(), plan, d_pcm, d_feat, nullptr), "Fbank::Process");
     lane.Download(fbank_feature->Data(), fbank_feature->Stride(), d_feat, PK_FBANK_DIM, sizeof(float), frames,
                   PK_FBANK_DIM);
   }

@@ -75,7 +75,13 @@ struct Runtime::Lane {
   void *stream = nullptr;
   std::mutex mu;
   DeviceBuffer scratch[kScratchSlots];
+  // the lane's model-less reusable plan (Lease::Plan) and its capacity
+  ce_gpu_plan *plan = nullptr;
+  int64_t plan_samples = 0;
 };
+
+// First capacity of a lane's plan: 4 s of audio, well above a streaming read.
+static constexpr int64_t kLanePlanSamples = 65536;
 
 static void copy2d(void *stream, hipMemcpyKind kind, void *dst, size_t dst_ld, const void *src, size_t src_ld,
                    size_t elem, size_t rows, size_t cols, const char *what) {
@@ -98,7 +104,10 @@ Runtime::Lane *Runtime::NewLane() {
   try {
     Check(ce_gpu_ctx_create(device_, l->stream, &l->ctx), "ce_gpu_ctx_create");
     Check(ce_gpu_ctx_set_fbank(l->ctx, fbank_mode_), "ce_gpu_ctx_set_fbank");
+    Check(ce_gpu_plan_create_reusable(l->ctx, nullptr, 1, kLanePlanSamples, 0, &l->plan), "ce_gpu_plan_create_reusable");
+    l->plan_samples = kLanePlanSamples;
   } catch (...) {
+    if (l->plan) ce_gpu_plan_destroy(l->plan);
     if (l->ctx) ce_gpu_ctx_destroy(l->ctx);
     hipStreamDestroy(s);
     throw;
@@ -166,6 +175,26 @@ int Runtime::lanes_created() const {
 ce_gpu_ctx *Runtime::Lease::ctx() const { return lane_->ctx; }
 DeviceBuffer &Runtime::Lease::scratch(int slot) { return lane_->scratch[slot]; }
 int Runtime::Lease::index() const { return lane_->index; }
+
+const ce_gpu_plan *Runtime::Lease::Plan(int64_t samples) {
+  Lane *l = lane_;
+  if (samples > l->plan_samples) {
+    // geometric growth, the only allocation left on the path.  The new plan's
+    // tables are written on the lane's stream behind whatever the old plan's
+    // launches left there; the old plan goes only once the new one exists
+    // (every drop-in call ends with a download that waits for the lane's
+    // stream, so none of its launches is still queued).
+    int64_t cap = l->plan_samples;
+    while (cap < samples) cap *= 2;
+    ce_gpu_plan *grown = nullptr;
+    Check(ce_gpu_plan_create_reusable(l->ctx, nullptr, 1, cap, 0, &grown), "ce_gpu_plan_create_reusable");
+    ce_gpu_plan_destroy(l->plan);
+    l->plan = grown;
+    l->plan_samples = cap;
+  }
+  Check(ce_gpu_plan_assign(l->plan, &samples, 1), "ce_gpu_plan_assign");
+  return l->plan;
+}
 
 void Runtime::Lease::Upload(void *dst, size_t dst_ld, const void *src, size_t src_ld, size_t elem, size_t rows,
                             size_t cols) {

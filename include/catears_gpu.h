@@ -86,7 +86,9 @@ const char *ce_gpu_last_error(void);
  * row steps in the matrix-core programs (ce_gpu_model_admit_row_ops,
  * ce_gpu_debug_rowop_chain, the config key gpu_row_ops), and so do the row
  * steps of a static int8 model that write the next layer's bytes
- * (ce_gpu_debug_rowop_chain_q, ce_gpu_debug_i8_static_launches). */
+ * (ce_gpu_debug_rowop_chain_q, ce_gpu_debug_i8_static_launches), and so do
+ * the reusable plans (ce_gpu_plan_create_reusable, ce_gpu_plan_assign,
+ * ce_gpu_plan_capacity, ce_gpu_debug_plan_tables). */
 const char *ce_gpu_version(void);
 
 /* ------------------------------------------------------------ context --- */
@@ -315,6 +317,15 @@ int ce_gpu_debug_fill_ctx(ce_gpu_ctx *ctx, uint32_t word, int64_t *bytes);
  * has rewritten them.  Any slot may be listed: a live slot's later rows are
  * then garbage by design.  n == 0 fills the per-push scratch alone. */
 int ce_gpu_debug_fill_sessions(ce_gpu_sessions *s, uint32_t word, int n, const int32_t *h_slots);
+/* Downloads one device table of a plan (either kind), for tests and tools:
+ * which = 0 sample_off, 1 frame_off (n_utt + 1 int64 each), 2 block_utt
+ * (int32 per fbank block, one word for none), 3 row_src, 4 row_dst (int32 per
+ * packed row), 5 row_edge (uint32 per packed row) -- the length the current
+ * assignment uses, not the capacity.  *bytes receives that length; h_out
+ * (capacity_bytes of room; NULL asks for the length alone) receives the
+ * words.  Synchronizes the plan's context first.  Measurement plumbing as
+ * above. */
+int ce_gpu_debug_plan_tables(const ce_gpu_plan *p, int which, void *h_out, int64_t capacity_bytes, int64_t *bytes);
 
 /* -------------------------------------------------------------- model --- */
 
@@ -615,6 +626,36 @@ int ce_gpu_plan_info(const ce_gpu_plan *p, int *n_utt, int64_t *total_samples,
 /* Per-utterance frame (= log-likelihood row) offsets, n_utt + 1 entries. */
 int ce_gpu_plan_frame_offsets(const ce_gpu_plan *p, int64_t *h_out);
 int ce_gpu_plan_destroy(ce_gpu_plan *p);
+
+/* A plan whose utterance lengths can be replaced.  Reserves, once, every
+ * device table and a ring of pinned descriptor buffers for any assignment of
+ * at most max_utts utterances and max_total_samples samples (and, with a
+ * model, any packing of those at max_rows; max_rows <= 0 selects 4096).
+ * Starts as the empty assignment (n_utt = 0).  Bound to ctx: use it only in
+ * calls on that context, and destroy it before the context.  CE_GPU_EINVAL
+ * for a non-positive max_utts or max_total_samples and for max_rows smaller
+ * than the model's L + R + 1.  Every entry that takes a const ce_gpu_plan *
+ * accepts a reusable plan. */
+int ce_gpu_plan_create_reusable(ce_gpu_ctx *ctx, const ce_gpu_model *model, int max_utts,
+                                int64_t max_total_samples, int max_rows, ce_gpu_plan **out);
+/* Replace the lengths: afterwards the plan equals what ce_gpu_plan_create
+ * gives for them (tables, chunks, ce_gpu_plan_info, frame offsets).  Ordered
+ * on the context's stream behind everything already enqueued with the old
+ * lengths.  Allocates, frees and synchronizes nothing: the host writes a
+ * descriptor of O(n_utt + segments) words and a kernel expands it into the
+ * tables.  The host blocks only when the ring entry it needs still has its
+ * copy in flight, that is, only when a ring's worth of assigns are all
+ * unfinished.  CE_GPU_EINVAL -- with the plan left at its previous assignment
+ * and nothing enqueued -- for n_utt < 0 or above max_utts, a negative length,
+ * more than max_total_samples samples in all, and for a plan that came from
+ * ce_gpu_plan_create. */
+int ce_gpu_plan_assign(ce_gpu_plan *p, const int64_t *h_num_samples, int n_utt);
+/* What ce_gpu_plan_create_reusable reserves for a model of context (left,
+ * right): the most frames, packed segments and packed rows of any assignment
+ * within the capacity.  Host arithmetic only: needs no GPU and touches none.
+ * Any output may be NULL. */
+int ce_gpu_plan_capacity(int max_utts, int64_t max_total_samples, int max_rows, int left, int right,
+                         int64_t *max_frames, int64_t *max_segments, int64_t *max_packed_rows);
 
 /* ------------------------------------------------------------ compute --- */
 

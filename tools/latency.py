@@ -9,7 +9,11 @@ bench's 4072-row batch.   python tools/latency.py [calls]
       the static int8 leg (ce_gpu_model_quantize_static, calibrated on 12 s of
       the synthetic audio): the 70-row chunk per call (LAT_ROWS for a sweep)
       with latency mode off and on, beside the bf16x6 latency mode, see
-      static_int8()"""
+      static_int8()
+
+  python tools/latency.py --fbank-stream [calls]
+      the drop-in Fbank::Process per 512-sample piece, alone and beside 4
+      concurrent AM lanes, see fbank_stream()"""
 import hashlib
 import json
 import os
@@ -232,9 +236,50 @@ def bf16(calls=300):
     print(json.dumps(res))
 
 
+def fbank_stream(calls=400):
+    """The drop-in Fbank::Process on a live stream: the host time of one call
+    on a 512-sample piece (32 ms of audio, the reference's ce_stt_process
+    read), through the native driver tests/native/pk_fbank_stream.cc (`make
+    host` builds catears_amd/lib/pk_fbank_stream).  Legs, one driver process
+    each, alone / beside / beside / alone: the fbank stream by itself, and
+    beside 4 threads that each stream frames through AcousticModel::Process
+    (TDNN-S, the config's chunk size) on lanes of their own (CATEARS_LANES=8,
+    so the fbank call never waits for a lane).  Per leg the median and the
+    10th / 90th percentile of the per-call wall time, the AM batches scored
+    meanwhile and what the library allocated and released during the timed
+    calls (ce_gpu_debug_counters).  One run times one drop-in library: the
+    directory of the driver and its libraries is CATEARS_PK_DIR (default:
+    this tree's catears_amd/lib); run this library and the parent's in
+    A B B A order."""
+    import subprocess
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    pk_dir = os.path.abspath(os.environ.get("CATEARS_PK_DIR") or os.path.join(root, "catears_amd", "lib"))
+    driver = os.path.join(pk_dir, "pk_fbank_stream")
+    mdir = os.path.join(tempfile.gettempdir(), f"catears_bench_{os.getuid()}")
+    conf = synth.write_model(mdir, "tdnn-s")
+    pcm_path = os.path.join(mdir, "fbank_stream.f32")
+    synth.pcm(7, 512 * (calls + 1)).tofile(pcm_path)
+    env = {**os.environ, "CATEARS_LANES": "8", "LD_LIBRARY_PATH": pk_dir + ":" + os.environ.get("LD_LIBRARY_PATH", "")}
+    res = {"driver": os.path.relpath(driver), "piece_samples": 512, "calls": calls}
+    for run, am_threads in enumerate((0, 4, 4, 0)):
+        r = subprocess.run([driver, "time", pcm_path, "512", str(calls + 1), conf, str(am_threads)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        if r.returncode != 0:
+            raise RuntimeError(f"{driver} failed ({r.returncode}): {r.stderr[-2000:]}")
+        rec = json.loads(r.stdout.strip().splitlines()[-1])
+        name = "alone" if am_threads == 0 else f"beside_{am_threads}_am_lanes"
+        res[f"fbank_process_512/{name}/run{run}"] = rec
+        print(f"Fbank::Process 512 samples {name:18s}: p50 {rec['p50_us']:7.1f} us  [{rec['p10_us']:.1f}, "
+              f"{rec['p90_us']:.1f}]  AM batches meanwhile {rec['am_batches_meanwhile']}  allocations "
+              f"{rec['device_allocs']} releases {rec['device_frees']}", flush=True)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
     nums = [int(v) for v in sys.argv[1:] if not v.startswith("--")]
-    if "--bf16" in sys.argv[1:]:
+    if "--fbank-stream" in sys.argv[1:]:
+        fbank_stream(*nums[:1])
+    elif "--bf16" in sys.argv[1:]:
         bf16(*nums[:1])
     elif "--static-int8" in sys.argv[1:]:
         static_int8(*nums[:1])
